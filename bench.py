@@ -28,10 +28,20 @@ proposals run beside step k's RoIPool without cross-stream waits (--streams 1
 serialises everything; --pool-on own puts the RoIPool on a stream of its own).
 Every step does all of its work.
 
-Prints ONE JSON line (rank 0): the metric of BASELINE.json, "roofline" (the
+Prints ONE JSON line (rank 0): the metric of BASELINE.json (images/sec and
+ms_per_step over the --steps timed steps).  A plain run does nothing else: it
+sets up, warms up, times the steps and prints the line ("roofline" and
+"cpu_baseline" are null).  --full adds, after the timed steps, "roofline" (the
 dominant kernel's algorithmic HBM bytes over its HIP-event time on its launch
-stream, vs the 8 TB/s peak) and "cpu_baseline" (the reference's CPU path on
-this host's cores, rank 0 at N=1 only).
+stream, vs the 8 TB/s peak, the kernel alone, the GPU's clock state under it),
+"cpu_baseline" (the reference's CPU path on this host's cores, rank 0 at N=1
+only) and, for N > 1, "strong_cfg3".
+
+--dump-outputs DIR writes what the last timed step computed (the arrays a
+caller of the step receives) as DIR/<name>.npy, float32 or float64; an array of
+more than 2^20 elements is written as a fixed, seeded sample of that many.  The
+inputs are seeded, so two builds run with the same arguments can be compared
+file by file.
 """
 from __future__ import annotations
 
@@ -121,8 +131,14 @@ def parse():
     ap.add_argument("--input-sets", type=int, default=0,
                     help="distinct input sets the steps cycle through (0 = enough for > 320 MiB, "
                          "i.e. more than the Infinity Cache; 1 = the same inputs every step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline record (the dominant kernel "
+                         "alone, the GPU's clock state), the CPU baseline and, for N > 1, strong_cfg3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; "
+                         "arrays of more than 2^20 elements as a fixed, seeded sample)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="bounded CPU-baseline sample (rank 0, N=1 only); 0 disables")
+                    help="with --full: bounded CPU-baseline sample (rank 0, N=1 only); 0 disables")
     ap.add_argument("--cpu-images", type=int, default=10, help="minimum timed CPU images (median)")
     return ap.parse_args()
 
@@ -620,6 +636,14 @@ def inference_step_fn(args, c, sets, base, world, n_total, backend, ev):
     step.gathered = gathered
     step.prop_out, step.pool_outs = prop_out, pool_outs  # (parity test: the per-stream buffers)
 
+    def last_outputs():  # the buffers the last step wrote (--dump-outputs)
+        j = (k_step[0] - 1) % nps
+        rois, idx, cnt = prop_out[j]
+        pooled, argmax, boxes = pool_outs[j if len(pool_outs) > 1 else 0]
+        return {"rois": rois, "anchor_idx": idx, "count": cnt, "boxes": boxes, "pooled": pooled,
+                "argmax": argmax}
+    step.last_outputs = last_outputs
+
     def alone():  # the dominant kernel by itself (after the timed steps): the last proposals
         ops.roi_pool_head(sets[0][2], prop_out[0][0].view(-1, 4), inds, 7, c["img_h"], c["img_w"],
                           rois_sorted=True, out=pool_outs[0])
@@ -757,6 +781,13 @@ def train_step_fn(args, c, sets, base, first_image, ev):
     step.state = state
     step.fixed = dict(rng=rng, grad=grad, boxes=boxes, labels=labels, anchors=anchors)
 
+    def last_outputs():  # what the last step returned to its caller (--dump-outputs)
+        names = {"lab": "anchor_labels", "reg_t": "anchor_reg_targets", "s_roi": "sample_rois",
+                 "s_reg": "sample_reg_targets", "s_lab": "sample_labels", "s_cnt": "sample_count",
+                 "bx": "boxes", "pooled": "pooled", "am": "argmax", "gi": "grad_features"}
+        return {name: state[k] for k, name in names.items()}
+    step.last_outputs = last_outputs
+
     def alone():  # the RoIPool backward by itself, on the last step's inputs
         ops._roi_pool_bwd(grad, state["bx"], state["am"], state["xshape"], 1.0)
     step.alone = alone
@@ -797,6 +828,103 @@ def strong_cfg3(args, world, rank, dev, backend, base_of):
     return {"workload": f"cfg3: {n_total} images sharded per image over {world} ranks (BASELINE configs[2])",
             "value": n_total * args.steps / el, "unit": "images/sec", "ms_per_step": el / args.steps * 1e3,
             "scaling": "strong", "global_batch": n_total, "images_per_gpu_max": len(mine)}
+
+
+DUMP_ELEMS = 1 << 20     # elements written per array: larger ones as a fixed, seeded sample
+DUMP_LIMIT = 64 << 20    # bytes written per run, all arrays together
+
+
+def dump_outputs(outs, path, rank):
+    """--dump-outputs: DIR/<name>.npy per output of the last timed step (ranks > 0:
+    <name>.rank<r>.npy), float64 as it is, everything else as float32 (the integer
+    outputs -- anchor indices, argmax, counts, labels -- are far below 2^24).  An array
+    of more than DUMP_ELEMS elements is written as its elements at DUMP_ELEMS sorted
+    flat indices drawn from a generator seeded with 0 (a function of its size alone)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in outs.items():
+        t = t.detach()
+        if t.numel() > DUMP_ELEMS:
+            pick = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+        a = t.cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MiB of outputs")
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
+def roofline_record(step, ev, train, cfg, rank, dev_index, alg_bytes, ms_step):
+    """--full: the dominant kernel's roofline record.  Its per-launch event intervals
+    come from the timed steps; the kernel alone and the GPU's clock state under it are
+    measured here, after them."""
+    # the dominant kernel (RoIPool fwd for inference, bwd for the training
+    # step: same algorithmic bytes -- features / grad_in once, rois, out +
+    # argmax / grad + argmax) runs once per step and each step moves its
+    # algorithmic bytes once, so the chip-level rate it sustains inside the
+    # pipeline is bytes per step / time per step (can only under-state the
+    # kernel: the step also holds the proposal chain)
+    achieved = alg_bytes / (ms_step * 1e-3) / 1e9
+    # per-launch HIP-event interval on the launch stream, for reference: the
+    # steps overlap on several streams, so this interval is shared with the
+    # neighbouring steps' kernels and is NOT a roofline time
+    ev_ms = float(np.mean([a.elapsed_time(b) for a, b in (ev["bwd"] if train else ev["fwd"])]))
+    fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev["fwd"]]))
+    # the same kernel with the chip to itself (after the timed region): 50
+    # back-to-back launches between two events on its launch stream
+    step.alone()
+    torch.cuda.synchronize()
+    a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    n_alone = 50
+    a0.record()
+    for _ in range(n_alone):
+        step.alone()
+    a1.record()
+    torch.cuda.synchronize()
+    alone_ms = a0.elapsed_time(a1) / n_alone
+    clocks = None
+    if rank == 0:  # the clock / power state under the same kernel: sampled while ~20 ms of it run
+        gs = GpuState(dev_index)
+        for _ in range(max(50, int(20.0 / max(alone_ms, 1e-3)))):
+            step.alone()
+        clocks = gs.sample()
+        torch.cuda.synchronize()
+        gs.close()
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "roi_pool_bwd_traffic.json" if train
+                         else "roi_pool_fwd_traffic.json")
+    if os.path.exists(tpath):
+        traffic = json.load(open(tpath)).get(cfg, {}).get("hbm_bytes_per_launch")
+    pool_roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                 "kernel": step.kernel,
+                 "basis": "pipeline-sustained: the kernel's algorithmic bytes per step / ms_per_step "
+                          "(one launch per step)",
+                 "alg_bytes_per_launch": alg_bytes,
+                 "kernel_us_alone": alone_ms * 1e3,
+                 "frac_alone": alg_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                 "alone_launches": n_alone,
+                 "gpu_state_during_alone": clocks,
+                 "event_interval_us_in_pipeline": ev_ms * 1e3}
+    if not train:
+        return pool_roof
+    # the training step's critical path is not an HBM kernel: the target
+    # creators' draws on numpy's sequential MT19937 stream, one chip-wide pass
+    # for both creators (frcnn_target_draws: draw_setup / _table / _group /
+    # _chain / _record kernels) on the draws' stream
+    dr = ev["draw"]  # the draws' stream period: one record per step after the draws
+    gaps = [a.elapsed_time(b) for a, b in zip(dr[:-1], dr[1:])]
+    draw_us = float(np.mean(gaps)) * 1e3 if gaps else None  # (--steps 1: no period)
+    pool_roof["fwd_event_interval_us_in_pipeline"] = fwd_ms * 1e3
+    return {"bound": "latency", "kernel": "draw_setup_kernel + draw_table_kernel (chip-wide draws)",
+            "unit": "us/step", "achieved": draw_us, "peak": None, "frac": None, "traffic": None,
+            "basis": "the draws' stream period (both target creators' draws as one chip-wide pass: the MT19937 "
+                     "state blocks twisted on one CU, per-segment step-count tables over the chip, their "
+                     "chain, the recorded swaps; + the stream's wait / record packets) between consecutive "
+                     "steps, HIP events; latency-bound, so no HBM / MFMA peak applies",
+            "draws_share_of_step": None if draw_us is None else draw_us / (ms_step * 1e3),
+            "roi_pool_bwd": pool_roof}
 
 
 def main():
@@ -867,72 +995,11 @@ def main():
     C, H, W = sets[0][2].shape[1:]
     alg_bytes = N * C * H * W * 4 + R * 20 + 2 * R * C * 49 * 4
     ms_step = el / args.steps * 1e3
-    # the dominant kernel (RoIPool fwd for inference, bwd for the training
-    # step: same algorithmic bytes -- features / grad_in once, rois, out +
-    # argmax / grad + argmax) runs once per step and each step moves its
-    # algorithmic bytes once, so the chip-level rate it sustains inside the
-    # pipeline is bytes per step / time per step (can only under-state the
-    # kernel: the step also holds the proposal chain)
-    achieved = alg_bytes / (ms_step * 1e-3) / 1e9
-    # per-launch HIP-event interval on the launch stream, for reference: the
-    # steps overlap on several streams, so this interval is shared with the
-    # neighbouring steps' kernels and is NOT a roofline time
-    ev_ms = float(np.mean([a.elapsed_time(b) for a, b in (ev["bwd"] if train else ev["fwd"])]))
-    fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in ev["fwd"]]))
-    # the same kernel with the chip to itself (after the timed region): 50
-    # back-to-back launches between two events on its launch stream
-    step.alone()
-    torch.cuda.synchronize()
-    a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    n_alone = 50
-    a0.record()
-    for _ in range(n_alone):
-        step.alone()
-    a1.record()
-    torch.cuda.synchronize()
-    alone_ms = a0.elapsed_time(a1) / n_alone
-    clocks = None
-    if rank == 0:  # the clock / power state under the same kernel: sampled while ~20 ms of it run
-        gs = GpuState(dev_index)
-        for _ in range(max(50, int(20.0 / max(alone_ms, 1e-3)))):
-            step.alone()
-        clocks = gs.sample()
-        torch.cuda.synchronize()
-        gs.close()
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "roi_pool_bwd_traffic.json" if train
-                         else "roi_pool_fwd_traffic.json")
-    if os.path.exists(tpath):
-        traffic = json.load(open(tpath)).get(cfg, {}).get("hbm_bytes_per_launch")
-    pool_roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                 "kernel": step.kernel,
-                 "basis": "pipeline-sustained: the kernel's algorithmic bytes per step / ms_per_step "
-                          "(one launch per step)",
-                 "alg_bytes_per_launch": alg_bytes,
-                 "kernel_us_alone": alone_ms * 1e3,
-                 "frac_alone": alg_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                 "alone_launches": n_alone,
-                 "gpu_state_during_alone": clocks,
-                 "event_interval_us_in_pipeline": ev_ms * 1e3}
-    if train:
-        # the training step's critical path is not an HBM kernel: the target
-        # creators' draws on numpy's sequential MT19937 stream, one chip-wide pass
-        # for both creators (frcnn_target_draws: draw_setup / _table / _group /
-        # _chain / _record kernels) on the draws' stream
-        dr = ev["draw"]  # the draws' stream period: one record per step after the draws
-        gaps = [a.elapsed_time(b) for a, b in zip(dr[:-1], dr[1:])]
-        draw_us = float(np.mean(gaps)) * 1e3 if gaps else None  # (--steps 1: no period)
-        pool_roof["fwd_event_interval_us_in_pipeline"] = fwd_ms * 1e3
-        roof = {"bound": "latency", "kernel": "draw_setup_kernel + draw_table_kernel (chip-wide draws)",
-                "unit": "us/step", "achieved": draw_us, "peak": None, "frac": None, "traffic": None,
-                "basis": "the draws' stream period (both target creators' draws as one chip-wide pass: the MT19937 "
-                         "state blocks twisted on one CU, per-segment step-count tables over the chip, their "
-                         "chain, the recorded swaps; + the stream's wait / record packets) between consecutive "
-                         "steps, HIP events; latency-bound, so no HBM / MFMA peak applies",
-                "draws_share_of_step": None if draw_us is None else draw_us / (ms_step * 1e3),
-                "roi_pool_bwd": pool_roof}
-        pool_roof = roof
+    if args.dump_outputs:  # before anything else reuses the last step's buffers
+        dump_outputs(step.last_outputs(), args.dump_outputs, rank)
+    pool_roof = None
+    if args.full:
+        pool_roof = roofline_record(step, ev, train, cfg, rank, dev_index, alg_bytes, ms_step)
     images = n_total * args.steps
     workload = workload_name(cfg, c, N, n_total, world, C, train)
     rec = {
@@ -960,14 +1027,14 @@ def main():
     }
     if gathered:
         rec["gathered_last_step"] = gathered
-    if world > 1 and args.config == "auto" and not args.host_io:
+    if args.full and world > 1 and args.config == "auto" and not args.host_io:
         # configs[2] as written (64 GLOBAL images sharded per image, strong scaling),
         # beside the weak-scaled headline: the same step code, its own inputs
         try:
             rec["strong_cfg3"] = strong_cfg3(args, world, rank, dev, backend, base_of=A)
         except Exception as e:  # noqa: BLE001 -- the headline line stands on its own
             rec["strong_cfg3"] = {"error": f"{type(e).__name__}: {str(e)[:200]}"}
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         rec["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds, args.cpu_images, train)
         rec["cpu_baseline"]["gpu_over_cpu"] = rec["value"] / rec["cpu_baseline"]["value"]
     if rank == 0:

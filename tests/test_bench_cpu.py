@@ -5,7 +5,10 @@ through the same config / sharding / naming code bench.py's ranks run."""
 import argparse
 import os
 import socket
+import sys
 
+import numpy as np
+import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
@@ -50,6 +53,36 @@ def test_auto_config_is_one_workload_at_every_n():
     assert len({r[1] for r in recs.values()}) == 1          # same workload string
     assert [recs[w][2] for w in (1, 2, 4, 8)] == [8, 16, 32, 64]  # N = 8: configs[2]'s 64 images
     assert recs[8][2] == synth.CONFIGS["cfg3"]["batch"]
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for; --steps / --warmup are taken as given."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    args = bench.parse()
+    assert (args.full, args.dump_outputs, args.steps, args.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_dump_outputs_format(tmp_path):
+    """One .npy per output, float64 kept, everything else float32; an array of more
+    than DUMP_ELEMS elements as the seeded sample, the same from call to call."""
+    n = 5 * (bench.DUMP_ELEMS // 4)
+    big = torch.arange(n, dtype=torch.float32).reshape(-1, 5)
+    outs = {"big": big, "idx": torch.tensor([[3, -1], [7, 9]], dtype=torch.int32),
+            "f64": torch.tensor([1.0 / 3.0], dtype=torch.float64)}
+    bench.dump_outputs(outs, str(tmp_path / "a"), 0)
+    bench.dump_outputs(outs, str(tmp_path / "b"), 1)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert sorted(a) == ["big.npy", "f64.npy", "idx.npy"]
+    assert sorted(b) == ["big.rank1.npy", "f64.rank1.npy", "idx.rank1.npy"]
+    assert a["idx.npy"].dtype == np.float32 and a["idx.npy"].tolist() == [[3.0, -1.0], [7.0, 9.0]]
+    assert a["f64.npy"].dtype == np.float64 and a["f64.npy"][0] == 1.0 / 3.0
+    pick = np.sort(np.random.default_rng(0).integers(0, n, bench.DUMP_ELEMS))
+    assert a["big.npy"].dtype == np.float32 and np.array_equal(a["big.npy"], pick.astype(np.float32))
+    assert np.array_equal(a["big.npy"], b["big.rank1.npy"])
 
 
 def test_two_gloo_ranks_name_the_n1_workload():

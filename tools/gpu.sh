@@ -6,7 +6,7 @@
 #   test [pytest args]         pytest -m gpu (all GPU tests when no args)
 #   smoke                      __graft_entry__.smoke()
 #   ab CFG VARIANTS [ARGS]     tools/ab_roi_pool.py (RoIPool forward paths, interleaved rounds)
-#   bench NAME [bench args]    bench.py -> OUT/bench_NAME.json
+#   bench NAME [bench args]    bench.py --full -> OUT/bench_NAME.json
 #   prof NAME [bench args]     rocprofv3 --kernel-trace --stats of bench.py -> OUT/prof_NAME
 #   alone CFG [LAUNCHES]       rocprofv3 of tools/pool_alone.py -> OUT/prof_alone_CFG
 #   pmc CFG KERNEL             PMC passes of tools/pmc_roi_pool.sh over bench CFG, summarised for KERNEL
@@ -33,7 +33,7 @@ run_step() {
       python3 -c "import json; s=open('$OUT/ab_$cfg.json').read(); d=json.loads(s[s.index('{'):]); print('$cfg', {k: round(v['us_median'],1) for k,v in d['variants'].items()})" ;;
     bench)
       local name=$1; shift
-      timeout -k 10 400 python -u bench.py "$@" > "$OUT/bench_$name.json" 2>"$OUT/bench_$name.err" || { tail -5 "$OUT/bench_$name.err"; return 1; }
+      timeout -k 10 400 python -u bench.py --full "$@" > "$OUT/bench_$name.json" 2>"$OUT/bench_$name.err" || { tail -5 "$OUT/bench_$name.err"; return 1; }
       python3 -c "import json; d=json.loads(open('$OUT/bench_$name.json').read().strip().splitlines()[-1]); r=d['roofline']; f=lambda v: None if v is None else round(v,3); print('$name', round(d['value'],1), 'img/s', round(d['ms_per_step']*1e3,1), 'us/step', r.get('kernel'), 'achieved', f(r.get('achieved')), 'frac', f(r.get('frac')), 'alone', f(r.get('kernel_us_alone')), f(r.get('frac_alone')))" ;;
     prof)
       local name=$1; shift

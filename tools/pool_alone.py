@@ -6,7 +6,7 @@ Builds the bench's inputs for the config (synthetic features, the batch's
 proposals), then issues the RoIPool forward of the step (RoI transform + pack +
 pool, one launch: nets/heads.py:42-48) -- or for cfg5 the RoIPool backward of a
 resident upstream gradient -- `--launches` times back to back on one stream,
-the same launch bench.py's `kernel_us_alone` times with HIP events.  Prints the
+the same launch `bench.py --full`'s `kernel_us_alone` times with HIP events.  Prints the
 event-timed mean per launch as JSON, so the rocprofv3 average of the same run
 can be checked against it.
 """

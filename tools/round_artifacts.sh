@@ -19,7 +19,7 @@ timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/
 bench() {  # name args...
   local name=$1; shift
   st "bench $name"
-  timeout -k 10 300 python -u bench.py "$@" > "$OUT/bench_$name.json" 2>"$OUT/bench_$name.err" || return $?
+  timeout -k 10 300 python -u bench.py --full "$@" > "$OUT/bench_$name.json" 2>"$OUT/bench_$name.err" || return $?
   tail -c 300 "$OUT/bench_$name.json"; echo
 }
 prof() {  # name args...
