@@ -316,6 +316,39 @@ int frcnn_target_draws(int N, int A, int G_at, int n_sample_at, double pos_ratio
 int frcnn_proposal_target_draw_status(int N, int Rp, int G, int n_sample, const void* workspace, size_t ws_bytes,
                                       int* out);
 
+/* -------------------------------------------------------------- detections */
+
+/* Head outputs -> detections, batched over N images: softmax, per-class box
+ * decode, score threshold, per-class NMS.  No reference counterpart: the
+ * reference stops at the head (nets/faster_rcnn.py:32, an empty test_eval.py).
+ * The contract is the py-faster-rcnn / chainer predict + _suppress convention
+ * the reference replicates, in this project's arithmetic (DESIGN.md
+ * "Detections"); class 0 is background and yields no detection.
+ *   rois   fp32 [N,R,4] [ymin,xmin,ymax,xmax] with rcount int32 [N] valid rows
+ *          per image (frcnn_propose's out_rois / out_count as they are; rcount
+ *          is clamped to [0,R], rows past it are ignored whatever they hold)
+ *   cls    fp32 [N,R,C] head logits (nets/heads.py:50 returns the [N,C,R] view)
+ *   reg    fp32 [N,R,4C], class c in columns 4c..4c+3
+ *   reg_mean / reg_std: HOST fp32 [4] (utils/utils.py:272)
+ *   1 <= R <= 1024, 2 <= C <= 128, max_det >= 1
+ * Per image and class c >= 1: p = softmax(cls) (ATen's last-dim order, exp
+ * correctly rounded); candidates p[r,c] > score_thresh; box = reg2bbox(rois[r],
+ * reg[r,4c:4c+4] * reg_std + reg_mean) clamped to the image as nets/rpn.py:62-63;
+ * NMS as frcnn_nms (ties by ascending r).  Non-finite boxes are outside the
+ * contract.  Outputs, class ascending then NMS keep order, padded to max_det:
+ *   det_boxes  fp32 [N,max_det,4]   padding 0
+ *   det_labels int32 [N,max_det]    class id 1..C-1, padding -1
+ *   det_scores fp32 [N,max_det]     padding 0
+ *   det_roi    int32 [N,max_det]    source row r, padding -1
+ *   det_count  int32 [N]            min(det_total, max_det)
+ *   det_total  int32 [N]            kept over all classes (<= R*(C-1)) */
+size_t frcnn_detect_workspace_size(int N, int R, int C);
+int frcnn_detect(int N, int R, int C, const float* rois, const int32_t* rcount, const float* cls,
+                 const float* reg, const float* reg_mean, const float* reg_std, float img_h,
+                 float img_w, float score_thresh, double nms_thresh, int max_det, float* det_boxes,
+                 int32_t* det_labels, float* det_scores, int32_t* det_roi, int32_t* det_count,
+                 int32_t* det_total, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,9 @@ SIGNATURES = {
     "frcnn_anchor_target_draw_status": (I32, [I32, I32, I32, P, SZ, P]),
     "frcnn_proposal_target_draw_status": (I32, [I32, I32, I32, I32, P, SZ, P]),
     "frcnn_target_draws": (I32, [I32, I32, I32, I32, F64, P, SZ, I32, I32, I32, F64, P, SZ, P, P, P]),
+    "frcnn_detect_workspace_size": (SZ, [I32, I32, I32]),
+    "frcnn_detect": (I32, [I32, I32, I32, P, P, P, P, P, P, F32, F32, F32, F64, I32, P, P, P, P, P, P,
+                           P, SZ, P]),
 }
 
 # diagnostic entry points of instrumented builds only (not in include/frcnn_capi.h)

@@ -21,69 +21,9 @@
 #include <cstring>
 
 #include "common.h"
+#include "nms_iou.h"
 
 namespace frcnn {
-
-// Exact form of torchvision's `(double)(inter / union) > iou_threshold`.
-struct NmsThr {
-    double thr;    // the raw threshold
-    double mid;    // midpoint below the smallest float T with (double)T > thr
-    int tie_incl;  // a quotient equal to `mid` rounds up to T
-    int never;     // thr is NaN: nothing is ever suppressed
-};
-
-static NmsThr make_thr(double thr) {
-    NmsThr t{};
-    t.thr = thr;
-    if (std::isnan(thr)) {
-        t.never = 1;
-        return t;
-    }
-    float f = static_cast<float>(thr);
-    if (!(static_cast<double>(f) > thr)) f = std::nextafter(f, INFINITY);
-    if (std::isinf(f) && f > 0) {
-        t.mid = std::ldexp(1.0, 128) - std::ldexp(1.0, 103);  // overflow boundary, ties to inf
-        t.tie_incl = 1;
-        return t;
-    }
-    float pred = std::nextafter(f, -INFINITY);
-    t.mid = (static_cast<double>(pred) + static_cast<double>(f)) * 0.5;
-    uint32_t bits;
-    std::memcpy(&bits, &f, 4);
-    t.tie_incl = (bits & 1u) == 0;
-    return t;
-}
-
-// IoU(a, b) > thr with torchvision's fp32 op order.
-// Fast path: RN(inter/uni) > thr  <=>  inter >= mid*uni  (exact in fp64, since
-// mid has <= 25 and uni 24 significant bits), valid for finite uni > 0.
-__device__ __forceinline__ bool iou_over(float4 a, float aarea, float4 b, float barea,
-                                         const NmsThr& t) {
-    float xx1 = a.x < b.x ? b.x : a.x;
-    float yy1 = a.y < b.y ? b.y : a.y;
-    float xx2 = b.z < a.z ? b.z : a.z;
-    float yy2 = b.w < a.w ? b.w : a.w;
-    float w = xx2 - xx1;
-    float h = yy2 - yy1;
-    w = 0.0f < w ? w : 0.0f;
-    h = 0.0f < h ? h : 0.0f;
-    float inter = w * h;
-    float uni = aarea + barea;
-    uni = uni - inter;
-    if (uni > 0.0f && uni <= FLT_MAX && inter <= FLT_MAX) {
-        double lhs = static_cast<double>(inter);
-        double rhs = t.mid * static_cast<double>(uni);
-        return lhs > rhs || (t.tie_incl && lhs == rhs);
-    }
-    float ovr = inter / uni;
-    return static_cast<double>(ovr) > t.thr;
-}
-
-__device__ __forceinline__ float box_area(float4 b) {
-    float dx = b.z - b.x;
-    float dy = b.w - b.y;
-    return dx * dy;
-}
 
 constexpr uint64_t kInvalidKey = ~0ull;
 

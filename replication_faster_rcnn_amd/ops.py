@@ -8,6 +8,9 @@
   ``total_loss.backward()`` at train.py:126).
 * ``propose(...)`` -- the batched proposal layer (nets/rpn.py:47-79 over all
   images at once, replacing the per-image loop nets/rpn.py:131-136).
+* ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
+  detections for the whole batch (no reference counterpart; DESIGN.md
+  "Detections").
 
 Inputs may live on the CPU (reference style); they are moved to the current
 HIP device, and results are returned on the input's device.  Errors follow
@@ -259,6 +262,77 @@ def propose(scores: torch.Tensor, deltas: torch.Tensor, *, img_w: float, img_h: 
                                  _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                "propose")
     return rois, idx, cnt
+
+
+# ----------------------------------------------------------------- detections
+REG_MEAN = (0.0, 0.0, 0.0, 0.0)   # utils/utils.py:272 (ProposalTargetCreator's normalisation)
+REG_STD = (0.1, 0.1, 0.2, 0.2)
+_detect_cache = {}  # host reg_mean / reg_std arrays + workspace size per shape (built once)
+
+
+def detect(rois: torch.Tensor, rcount: torch.Tensor, cls: torch.Tensor, reg: torch.Tensor, *,
+           img_h: float, img_w: float, score_thresh: float = 0.05, nms_thresh: float = 0.3,
+           reg_mean=REG_MEAN, reg_std=REG_STD, max_det: int = None, out=None, workspace=None):
+    """Head outputs -> detections on device tensors (frcnn_detect; DESIGN.md
+    "Detections" is the contract): softmax, per-class decode, score threshold
+    and per-class NMS for the whole batch.
+
+    rois fp32 [N, R, 4] + rcount int32 [N] (``RPN.rois_padded`` / ``rois_count``
+    as they are), cls fp32 [N, R, C] logits (``ResnetHead`` returns the
+    ``[N, C, R]`` view: pass ``cls.permute(0, 2, 1).contiguous()``), reg fp32
+    [N, R, 4C].  Returns padded (det_boxes [N, max_det, 4], det_labels int32
+    [N, max_det], det_scores [N, max_det], det_roi int32 [N, max_det], det_count
+    int32 [N], det_total int32 [N]) -- no host synchronisation.  ``max_det``
+    defaults to R*(C-1), which never truncates.
+    """
+    lib = _lib.load()
+    for name, t, dt in (("rois", rois, torch.float32), ("rcount", rcount, torch.int32),
+                        ("cls", cls, torch.float32), ("reg", reg, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError(f"detect: {name} must be a contiguous {dt} device tensor")
+    if cls.dim() != 3:
+        raise RuntimeError(f"detect: cls must be [N, R, C]; got {tuple(cls.shape)}")
+    N, R, C = cls.shape
+    if tuple(rois.shape) != (N, R, 4) or tuple(rcount.shape) != (N,) or tuple(reg.shape) != (N, R, 4 * C):
+        raise RuntimeError(f"detect: rois {tuple(rois.shape)} / rcount {tuple(rcount.shape)} / reg "
+                           f"{tuple(reg.shape)} do not match cls {tuple(cls.shape)}")
+    if max_det is None:
+        max_det = R * (C - 1)
+    max_det = int(max_det)
+    dev = cls.device
+    key = (N, R, C, tuple(float(v) for v in reg_mean), tuple(float(v) for v in reg_std))
+    cached = _detect_cache.get(key)
+    if cached is None:
+        if len(key[3]) != 4 or len(key[4]) != 4:
+            raise RuntimeError("detect: reg_mean and reg_std must have 4 values")
+        cached = ((_lib.F32 * 4)(*key[3]), (_lib.F32 * 4)(*key[4]),
+                  int(lib.frcnn_detect_workspace_size(N, R, C)))
+        _detect_cache[key] = cached
+    mean, std, need = cached
+    if out is None:
+        out = (torch.empty((N, max_det, 4), dtype=torch.float32, device=dev),
+               torch.empty((N, max_det), dtype=torch.int32, device=dev),
+               torch.empty((N, max_det), dtype=torch.float32, device=dev),
+               torch.empty((N, max_det), dtype=torch.int32, device=dev),
+               torch.empty((N,), dtype=torch.int32, device=dev),
+               torch.empty((N,), dtype=torch.int32, device=dev))
+    else:  # caller-owned outputs (static buffers of a captured HIP graph)
+        want = [((N, max_det, 4), torch.float32), ((N, max_det), torch.int32), ((N, max_det), torch.float32),
+                ((N, max_det), torch.int32), ((N,), torch.int32), ((N,), torch.int32)]
+        if len(out) != 6 or any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous()
+                                for t, (s, d) in zip(out, want)):
+            raise RuntimeError("detect: out buffers must be fp32 [N,max_det,4], int32 [N,max_det], "
+                               "fp32 [N,max_det], int32 [N,max_det], int32 [N], int32 [N]")
+    ws = workspace if workspace is not None else _lib.cached_workspace("detect", need, dev)
+    if need and ws.numel() < need:
+        raise RuntimeError(f"detect: workspace of {ws.numel()} B < {need} B")
+    boxes, labels, scores, roi, count, total = out
+    _lib.check(lib.frcnn_detect(N, R, C, _lib.ptr(rois), _lib.ptr(rcount), _lib.ptr(cls), _lib.ptr(reg),
+                                mean, std, float(img_h), float(img_w), float(score_thresh),
+                                float(nms_thresh), max_det, _lib.ptr(boxes), _lib.ptr(labels),
+                                _lib.ptr(scores), _lib.ptr(roi), _lib.ptr(count), _lib.ptr(total),
+                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "detect")
+    return boxes, labels, scores, roi, count, total
 
 
 # ------------------------------------------------------------- RPN epilogue

@@ -48,6 +48,50 @@ def features(C: int, H: int, W: int, seed: int, image_index: int) -> np.ndarray:
     return r.standard_normal((C, H, W), dtype=np.float32)
 
 
+def head_outputs(N: int, R: int, C: int, img_h: int, img_w: int, seed: int, first_image: int = 0,
+                 objects: int = 6):
+    """Second-stage inputs of ``ops.detect`` for images ``first_image ..
+    first_image+N-1``: (rois fp32 [N,R,4], rcount int32 [N] = R, cls fp32
+    [N,R,C] logits, reg fp32 [N,R,4C]).  Per image, ``objects`` boxes with a
+    class in 1..C-1 each; two RoIs in three sit on an object (position and size
+    jittered), the rest are background boxes anywhere.  Logits are N(0,1), the
+    object's class raised by N(5,2), the background class by 3 on background
+    RoIs; reg is N(0,0.5)."""
+    rois = np.empty((N, R, 4), np.float32)
+    cls = np.empty((N, R, C), np.float32)
+    reg = np.empty((N, R, 4 * C), np.float32)
+    for i in range(N):
+        r = rng_for(seed, first_image + i, 4)
+        cy = r.uniform(0.15, 0.85, objects) * img_h
+        cx = r.uniform(0.15, 0.85, objects) * img_w
+        oh = r.uniform(0.15, 0.5, objects) * img_h
+        ow = r.uniform(0.15, 0.5, objects) * img_w
+        ocls = r.integers(1, C, objects)
+        share = r.dirichlet(np.full(objects, 2.0))
+        obj = np.where(r.uniform(size=R) < 2.0 / 3.0, r.choice(objects, size=R, p=share), -1)
+        y = np.sort(r.uniform(0, img_h, (R, 2)), axis=1)
+        x = np.sort(r.uniform(0, img_w, (R, 2)), axis=1)
+        box = np.stack([y[:, 0], x[:, 0], np.maximum(y[:, 1], y[:, 0] + 16), np.maximum(x[:, 1], x[:, 0] + 16)], 1)
+        on = obj >= 0
+        jit = r.standard_normal((R, 4))
+        h = oh[obj] * np.exp(0.15 * jit[:, 2])
+        w = ow[obj] * np.exp(0.15 * jit[:, 3])
+        yy = cy[obj] + 0.1 * oh[obj] * jit[:, 0]
+        xx = cx[obj] + 0.1 * ow[obj] * jit[:, 1]
+        obox = np.stack([yy - h / 2, xx - w / 2, yy + h / 2, xx + w / 2], 1)
+        box = np.where(on[:, None], obox, box)
+        box[:, [0, 2]] = np.clip(box[:, [0, 2]], 0, img_h)
+        box[:, [1, 3]] = np.clip(box[:, [1, 3]], 0, img_w)
+        logit = r.standard_normal((R, C))
+        rows = np.arange(R)
+        logit[rows[on], ocls[obj[on]]] += 5.0 + 2.0 * r.standard_normal(int(on.sum()))
+        logit[rows[~on], 0] += 3.0
+        rois[i] = box
+        cls[i] = logit
+        reg[i] = 0.5 * r.standard_normal((R, 4 * C))
+    return rois, np.full((N,), R, np.int32), cls, reg
+
+
 def gt_boxes(img_h: int, img_w: int, G: int, seed: int, image_index: int, n_valid=None):
     """32-slot padded gt like ``utils/data_loader.py:88-115``: layout
     ``[ymin, xmin, ymax, xmax]`` fp64, ``np.around``-ed; padded rows are -1
