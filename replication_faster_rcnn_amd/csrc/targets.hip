@@ -800,12 +800,15 @@ __global__ __launch_bounds__(kSampThreads) void at_sample_kernel(
 
 // grid (ceil(A/256), N): final label (after disabling) and regression target
 // bbox2reg(anchor, bbox[argmax]) (utils/utils.py:75-100,146-150; anchor stats
-// fp32, box stats fp64).
+// fp32, box stats fp64).  An image without a positive label gets zeros
+// (utils/utils.py:149-150): no gt, or a positives' call that disabled them all
+// (calls[2n] = (cnt, k = cnt, ..): int(pos_ratio * n_sample) == 0).
 __global__ __launch_bounds__(256) void at_finish_kernel(
     const float* __restrict__ anchors, int A, const double* __restrict__ gt,
     const int* __restrict__ gcount, int Gp, const int32_t* __restrict__ row_arg,
     const int8_t* __restrict__ label0, const uint8_t* __restrict__ keep,
-    const int* __restrict__ sampled, int32_t* __restrict__ label, double* __restrict__ reg) {
+    const int* __restrict__ sampled, const int4* __restrict__ calls, int32_t* __restrict__ label,
+    double* __restrict__ reg) {
     const int n = blockIdx.y;
     const int a = blockIdx.x * 256 + threadIdx.x;
     if (a >= A) return;
@@ -817,7 +820,12 @@ __global__ __launch_bounds__(256) void at_finish_kernel(
     label[o] = l;
     const int G = gcount[n];
     double* r = reg + o * 4;
-    if (G == 0) {
+    bool none = G == 0;
+    if (!none && sampled[2 * n]) {
+        const int4 c = calls[2 * n];
+        none = c.y == c.x;
+    }
+    if (none) {
         r[0] = r[1] = r[2] = r[3] = 0.0;
         return;
     }
@@ -2145,7 +2153,7 @@ extern "C" int frcnn_anchor_target_finish(int N, int A, int G, const float* anch
     FRCNN_LAUNCH_CHECK("samp_emit_kernel");
     const int nblk = (A + 255) / 256;
     hipLaunchKernelGGL(at_finish_kernel, dim3(nblk, N), dim3(256), 0, st, anchors, A, w.gt, w.gcount,
-                       Gp, w.row_arg, w.label0, w.keep, w.sampled, label, reg);
+                       Gp, w.row_arg, w.label0, w.keep, w.sampled, w.calls, label, reg);
     FRCNN_LAUNCH_CHECK("at_finish_kernel");
     if (argmax && hipMemcpyAsync(argmax, w.row_arg, sizeof(int32_t) * N * A,
                                  hipMemcpyDeviceToDevice, st) != hipSuccess)

@@ -31,7 +31,9 @@ def _gt(boxes, labels, dev):
 def anchor_targets(boxes, labels, anchors, n_sample=256, pos_iou_thresh=0.7, neg_iou_thresh=0.3,
                    pos_ratio=0.5, sample=True, internals=False, rng=None):
     """boxes [N,G,4] fp64 (label -1 rows = padding), labels [N,G], anchors [A,4]
-    -> reg fp64 [N,A,4], label int32 [N,A] (device tensors)."""
+    -> reg fp64 [N,A,4], label int32 [N,A] (device tensors).  An image that keeps
+    no positive label (no gt, or int(pos_ratio * n_sample) == 0) gets all-zero
+    targets, as utils/utils.py:146-150 returns zeros there."""
     lib = _lib.load()
     dev = _lib.device()
     b, l = _gt(boxes, labels, dev)

@@ -107,7 +107,8 @@ def bbox2reg(anchors, bbox):
 
 class AnchorTargetCreator(object):
     """utils/utils.py:122-204; __call__(bbox, anchor) -> (reg, label) with the
-    reference's types (fp64 reg / int32 label, fp32 zeros without gt) and the
+    reference's types (fp64 reg / int32 label; fp32 zeros when no label is
+    positive: no gt, or int(pos_ratio * n_sample) == 0) and the
     same consumption of numpy's global RNG."""
 
     def __init__(self, n_sample=256, pos_iou_thresh=0.7, neg_iou_thresh=0.3, pos_ratio=0.5):
@@ -124,8 +125,9 @@ class AnchorTargetCreator(object):
             bb, lab, anchor, n_sample=self.n_sample, pos_iou_thresh=self.pos_iou_thresh,
             neg_iou_thresh=self.neg_iou_thresh, pos_ratio=self.pos_ratio, internals=True)
         label = label[0].cpu().numpy()
-        if bb.shape[1] == 0:
-            reg_np = np.zeros_like(np.asarray(anchor, np.float32))
+        if not (label > 0).any():   # utils/utils.py:146-150: no gt, or int(pos_ratio * n_sample) == 0
+            a = anchor.detach().cpu().numpy() if isinstance(anchor, torch.Tensor) else np.asarray(anchor)
+            reg_np = np.zeros_like(np.asarray(a, np.float32))
         else:
             reg_np = reg[0].cpu().numpy()
         if return_internals:

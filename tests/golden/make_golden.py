@@ -5,6 +5,11 @@ on the GPU box):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 
+or, for tests/golden/targets_edges.npz alone (the case table of
+tests/target_cases.py through the genuine creators):
+
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py target_edges
+
 The reference modules utils/anchors.py, utils/utils.py, nets/rpn.py and
 nets/heads.py are imported read-only (no bytecode is written) with
 tests/golden/_tvstub standing in for torchvision, which the reference imports
@@ -248,6 +253,59 @@ def gen_targets():
 
 
 # ---------------------------------------------------------------------------
+def _small_int(a):
+    a = np.asarray(a)
+    for t in (np.int8, np.uint8, np.int16, np.int32):
+        if a.size == 0 or (a.min() >= np.iinfo(t).min and a.max() <= np.iinfo(t).max):
+            return a.astype(t)
+    return a.astype(np.int64)
+
+
+def gen_target_edges():
+    """tests/target_cases.py through the genuine creators, one image at a time as
+    train.py does, constructor arguments and MT19937 seed per case.  A case the
+    reference raises on is left out (its name goes to ``left_out``)."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import warnings
+    import target_cases as tc
+    res, done, left_out = {}, [], []
+    for case in tc.ALL_CASES:
+        one = {}
+        np.random.seed(case.seed)
+        try:
+            with warnings.catch_warnings(), np.errstate(all="ignore"):
+                warnings.simplefilter("ignore")
+                for i in range(len(case.boxes)):
+                    k = f"{case.name}__{i}__"
+                    if case.kind == "anchor":
+                        at = ref_utils.AnchorTargetCreator(**case.kw)
+                        box = case.gt(i)
+                        argmax_ious, max_ious, _ = at._calc_ious(case.anchors, box)   # no RNG use
+                        reg, lab = at(box, case.anchors)
+                        one[k + "label"] = _small_int(lab)
+                        one[k + "argmax"] = _small_int(argmax_ious)
+                        one[k + "maxiou_sha"] = np.array(sha(np.asarray(max_ious, np.float64)))
+                        one[k + "reg_pos"] = np.asarray(reg)[lab == 1]
+                        one[k + "reg_dtype"] = np.array(str(reg.dtype))
+                        one[k + "reg_zero"] = np.array(not np.asarray(reg).any())
+                    else:
+                        pt = ref_utils.ProposalTargetCreator(**case.kw)
+                        roi, box, gl = case.image(i)
+                        s_roi, s_reg, s_lab = pt(torch.from_numpy(roi), box, gl, *case.norm)
+                        one[k + "roi"], one[k + "reg"], one[k + "label"] = s_roi, s_reg, s_lab
+                    st = np.random.get_state()
+                    one[k + "rng_pos"] = np.array(st[2])
+                    one[k + "rng_key_sha"] = np.array(sha(st[1]))
+        except Exception as e:  # noqa: BLE001
+            print(f"{case.name}: the reference raised {type(e).__name__}: {e} -- left out")
+            left_out.append(case.name)
+            continue
+        res.update(one)
+        done.append(case.name)
+    save("targets_edges.npz", cases=np.array(done), left_out=np.array(left_out, dtype="U32"), **res)
+
+
+# ---------------------------------------------------------------------------
 def gen_roi_pool():
     """nets/heads.py:27-59 genuine forward (RoI transform + [idx, box] pack),
     roi_pool arithmetic from the restatement; backward from the restatement."""
@@ -285,9 +343,13 @@ def gen_roi_pool():
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["target_edges"]:
+        gen_target_edges()
+        sys.exit(0)
     gen_anchors()
     gen_reg2bbox()
     nms_cases()
     gen_roi_pool()
     gen_proposals()
     gen_targets()
+    gen_target_edges()

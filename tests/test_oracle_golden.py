@@ -1,6 +1,8 @@
 """Pin the oracle (CPU restatement) against fixtures the genuine reference
 produced (tests/golden/make_golden.py).  CPU only."""
 import hashlib
+import os
+import sys
 
 import numpy as np
 import torch
@@ -8,6 +10,10 @@ import pytest
 
 from oracle import ref_numpy as orc
 from replication_faster_rcnn_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import target_cases as tc  # noqa: E402
 
 
 def sha(a):
@@ -124,6 +130,37 @@ def test_targets_vs_reference(golden, tag):
         assert np.array_equal(np.random.get_state()[1], g["rng_key_out"])
     finally:
         np.random.set_state(saved)
+
+
+@pytest.mark.parametrize("name", [c.name for c in tc.ALL_CASES])
+def test_target_edges_vs_reference(golden, name):
+    """The oracle on the edge-case table (tests/target_cases.py: ties, exact
+    thresholds, interleaved padding, size edges, non-finite boxes, non-default
+    sampling parameters and normalisation) against the genuine creators'
+    outputs in targets_edges.npz, compared as test_targets_vs_reference does:
+    labels, argmax, samples, regression targets and the RNG stream bit-exact.
+    The reference raised on no case (``nonfinite`` included: numpy only warns),
+    so every case of the table is pinned; one it raised on would be listed in
+    the file's ``left_out`` and stay an oracle-vs-device case only."""
+    g = golden("targets_edges.npz")
+    assert g["left_out"].size == 0 and sorted(g["cases"].tolist()) == sorted(c.name for c in tc.ALL_CASES)
+    case = tc.BY_NAME[name]
+    out = tc.oracle(case)
+    for i, im in enumerate(out["images"]):
+        k = f"{name}__{i}__"
+        if case.kind == "anchor":
+            assert np.array_equal(im["label"], g[k + "label"])
+            assert np.array_equal(im["argmax"], g[k + "argmax"])
+            assert sha(im["max_iou"]) == str(g[k + "maxiou_sha"])
+            assert str(im["reg"].dtype) == str(g[k + "reg_dtype"])
+            assert (not im["reg"].any()) == bool(g[k + "reg_zero"])
+            assert np.array_equal(im["reg"][im["label"] == 1], g[k + "reg_pos"], equal_nan=True)
+        else:
+            assert np.array_equal(im["roi"], g[k + "roi"])
+            assert np.array_equal(im["reg"], g[k + "reg"], equal_nan=True)
+            assert np.array_equal(im["label"], g[k + "label"])
+        assert im["rng_pos"] == int(g[k + "rng_pos"])
+        assert sha(im["rng_key"]) == str(g[k + "rng_key_sha"])
 
 
 @pytest.mark.parametrize("K,H,W", [(9, 38, 38), (15, 7, 11)])
