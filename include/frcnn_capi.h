@@ -349,6 +349,54 @@ int frcnn_detect(int N, int R, int C, const float* rois, const int32_t* rcount, 
                  int32_t* det_labels, float* det_scores, int32_t* det_roi, int32_t* det_count,
                  int32_t* det_total, void* workspace, size_t ws_bytes, void* stream);
 
+/* -------------------------------------------------------------- evaluation */
+
+/* One batch of detections scored against its ground truth and appended to a
+ * device-resident accumulator.  No reference counterpart: the reference's
+ * test_eval.py is an empty file.  The contract is the VOC devkit's voc_eval in
+ * this project's arithmetic (DESIGN.md "Evaluation").
+ *   det_boxes fp32 [N,M,4], det_labels int32 [N,M], det_scores fp32 [N,M],
+ *   det_count int32 [N]: frcnn_detect's outputs as they are (det_count is
+ *   clamped to [0,M]; slots past it are ignored whatever they hold)
+ *   gt_boxes fp64 [N,G,4] [ymin,xmin,ymax,xmax]; gt_labels int32 [N,G], a row is
+ *   valid when its label is in 1..C-1; gt_difficult uint8 [N,G] or NULL (none)
+ *   1 <= N <= 1024, 1 <= M <= 2^20, 0 <= G <= 256, 2 <= C <= 128, 1 <= cap <= 2^24
+ * Every slot below the clamped count becomes one record, in (image, slot)
+ * order.  A detection's gt is the first maximum of bbox_iou (utils/utils.py:
+ * 102-119, fp64; with plus_one, 1.0 added to columns 2, 3 of both boxes) over the
+ * valid gt of its class; it is matched when that IoU > iou_thresh.  Flag: 0 not
+ * matched (FP), -1 matched to a difficult gt or label outside 1..C-1 (ignored),
+ * else 1 (TP) for the gt's first claimant in (descending score, ascending slot)
+ * order and 0 for the others.  State (caller-owned, all zero = empty):
+ *   hdr       int64 [4+C]   n_records, n_images, batches dropped, 0, npos[0..C)
+ *   rec_key   uint64 [cap]  class << 56 | desc_score_key(score) << 24 | record index
+ *   rec_flag  int8 [cap]
+ *   rec_image int32 [cap]   n_images before the batch + n
+ * A batch that does not fit in cap writes nothing and adds one to hdr[2]; that
+ * is not an error (nothing is read back). */
+int frcnn_eval_update(int N, int M, int G, int C, int64_t cap, const float* det_boxes,
+                      const int32_t* det_labels, const float* det_scores, const int32_t* det_count,
+                      const double* gt_boxes, const int32_t* gt_labels, const uint8_t* gt_difficult,
+                      double iou_thresh, int plus_one, int64_t* hdr, uint64_t* rec_key, int8_t* rec_flag,
+                      int32_t* rec_image, void* stream);
+
+/* Per-class AP and mAP of an accumulator (once per dataset; the empty
+ * test_eval.py again, DESIGN.md "Evaluation" "Result").  n_records is hdr[0],
+ * read back by the caller.  The first n_records keys are sorted ascending
+ * (class, descending score, insertion order) inside the library; per class
+ * c >= 1 integer running TP / FP sums, rec = tp / npos[c], prec = tp / max(tp +
+ * fp, 1), then the 11-point AP (use_07_metric != 0) or the area under the
+ * precision envelope.  ap[c] = NaN for c = 0 and where npos[c] == 0; map = mean
+ * of the non-NaN entries.
+ *   ap double [C], map double [1]: device
+ *   sorted_key uint64 [n_records] (device) or NULL: the sorted keys
+ * Workspace: frcnn_eval_ap_workspace_size(C, cap) bytes serve every n_records
+ * <= cap (0 for a C or cap outside frcnn_eval_update's limits). */
+size_t frcnn_eval_ap_workspace_size(int C, int64_t cap);
+int frcnn_eval_ap(int C, int64_t n_records, const int64_t* hdr, const uint64_t* rec_key,
+                  const int8_t* rec_flag, int use_07_metric, double* ap, double* map,
+                  uint64_t* sorted_key, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

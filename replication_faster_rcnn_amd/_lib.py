@@ -86,6 +86,9 @@ SIGNATURES = {
     "frcnn_detect_workspace_size": (SZ, [I32, I32, I32]),
     "frcnn_detect": (I32, [I32, I32, I32, P, P, P, P, P, P, F32, F32, F32, F64, I32, P, P, P, P, P, P,
                            P, SZ, P]),
+    "frcnn_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, F64, I32, P, P, P, P, P]),
+    "frcnn_eval_ap_workspace_size": (SZ, [I32, I64]),
+    "frcnn_eval_ap": (I32, [I32, I64, P, P, P, I32, P, P, P, P, SZ, P]),
 }
 
 # diagnostic entry points of instrumented builds only (not in include/frcnn_capi.h)

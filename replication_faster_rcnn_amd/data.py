@@ -79,6 +79,27 @@ def get_labels(doc: dict, difficult: bool = False, n_obj: int = 32, class2num=CL
     return np.array(labels), np.around(boxes)
 
 
+def get_difficult(doc: dict, n_obj: int = 32, class2num=CLASS2NUM) -> np.ndarray:
+    """The ``difficult`` flag ``voc_data._get_labels`` (utils/data_loader.py:81-117)
+    folds into ``label = -1`` or drops, kept for the evaluator: uint8 [n_obj], 1
+    where that object's ``difficult`` tag is ``"1"``.  Rows line up with
+    ``get_labels(doc, difficult=True)``; a row that call marks -1 (unknown class,
+    unparsable bndbox, the single-``<object>`` quirk, padding) is 0."""
+    flags = np.zeros(n_obj, np.uint8)
+    objects = doc["annotation"]["object"]
+    for obj_ind, obj in enumerate(objects):
+        if obj_ind >= n_obj:
+            break
+        try:
+            class2num[obj["name"]]
+            bb = obj["bndbox"]
+            [float(bb[k]) for k in ("ymin", "xmin", "ymax", "xmax")]
+            flags[obj_ind] = 1 if obj.get("difficult") == "1" else 0
+        except Exception:  # the rows get_labels' bare except marks -1
+            flags[obj_ind] = 0
+    return flags
+
+
 def rescale_boxes(box: np.ndarray, image_hw, new_size=(600, 600)) -> np.ndarray:
     """utils/data_loader.py:63-70: rows (cols 0,2) by image height, cols 1,3 by
     width, in f64 (divide, then multiply); negative entries -> -1.  Returns a
@@ -91,9 +112,16 @@ def rescale_boxes(box: np.ndarray, image_hw, new_size=(600, 600)) -> np.ndarray:
     return b
 
 
-def load_targets(xml_text: str, image_hw, new_size=(600, 600), difficult=False, n_obj=32):
-    """One ``voc_data.__getitem__``'s (box, label) pair (image handling aside)."""
-    label, box = get_labels(parse_voc_annotation(xml_text), difficult=difficult, n_obj=n_obj)
+def load_targets(xml_text: str, image_hw, new_size=(600, 600), difficult=False, n_obj=32,
+                 return_difficult=False):
+    """One ``voc_data.__getitem__``'s (box, label) pair (image handling aside).
+    With ``return_difficult`` also ``get_difficult``'s flags: (box, label,
+    difficult) -- an evaluator wants ``difficult=True`` with it, so that the
+    difficult objects stay in as gt rows."""
+    doc = parse_voc_annotation(xml_text)
+    label, box = get_labels(doc, difficult=difficult, n_obj=n_obj)
+    if return_difficult:
+        return rescale_boxes(box, image_hw, new_size), label, get_difficult(doc, n_obj=n_obj)
     return rescale_boxes(box, image_hw, new_size), label
 
 

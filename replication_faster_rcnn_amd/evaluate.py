@@ -1,0 +1,77 @@
+"""PASCAL VOC evaluation of the detector on the device.
+
+The reference stops before this stage (its ``test_eval.py`` is an empty
+file); the protocol is the VOC devkit's ``voc_eval``, stated as a contract in
+DESIGN.md "Evaluation".  ``VOCEvaluator.update`` scores one inference batch
+against its ground truth with ``ops.eval_update`` -- stream-ordered, no
+allocation, no host read -- and ``result`` closes the dataset with
+``ops.eval_ap``: the only place that synchronises.
+
+    ev = VOCEvaluator()
+    for x, gt_boxes, gt_labels, gt_difficult in loader:
+        model.predict(x, width, height)
+        ev.update(model.last_detections, gt_boxes, gt_labels, gt_difficult)
+    print(ev.result()["map"])
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+
+def _dev(a, dtype):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return ops._to_dev(t, dtype)
+
+
+class VOCEvaluator:
+    """Accumulates TP / FP / ignored records of every detection in device
+    arrays of ``capacity`` records (``ops.eval_state``), for ``n_class`` classes
+    with class 0 the background.  ``plus_one`` is the devkit's pixel
+    convention (+1 on box heights and widths), ``use_07_metric`` its 11-point
+    AP instead of the area under the precision envelope."""
+
+    def __init__(self, n_class: int = 21, capacity: int = 1 << 20, iou_thresh: float = 0.5,
+                 use_07_metric: bool = False, plus_one: bool = True):
+        self.n_class = int(n_class)
+        self.capacity = int(capacity)
+        self.iou_thresh = float(iou_thresh)
+        self.use_07_metric = bool(use_07_metric)
+        self.plus_one = bool(plus_one)
+        self.state = ops.eval_state(self.n_class, self.capacity)
+
+    def reset(self) -> None:
+        """Back to the empty state (the record arrays need no clearing)."""
+        self.state[0].zero_()
+
+    def update(self, det, gt_boxes, gt_labels, gt_difficult=None) -> None:
+        """One batch.  ``det``: the tuple ``ops.detect`` returns or
+        ``FasterRCNN.last_detections``.  gt as the loader yields it: boxes
+        [N, G, 4] and labels [N, G] of any real dtype (the loader's fp64 labels
+        are converted; rows outside 1..n_class-1, such as its -1 padding, are
+        no gt), ``gt_difficult`` [N, G] or None; numpy arrays and CPU tensors
+        are moved to the device.  Nothing is read back."""
+        if len(det) == 6:
+            det = (det[0], det[1], det[2], det[4])
+        if len(det) != 4:
+            raise RuntimeError("VOCEvaluator.update: det must be ops.detect's 6-tuple or (boxes, labels, scores, "
+                               "count)")
+        det = tuple(_dev(t, dt) for t, dt in zip(det, (torch.float32, torch.int32, torch.float32, torch.int32)))
+        ops.eval_update(det, _dev(gt_boxes, torch.float64), _dev(gt_labels, torch.int32),
+                        None if gt_difficult is None else _dev(gt_difficult, torch.uint8),
+                        state=self.state, iou_thresh=self.iou_thresh, plus_one=self.plus_one)
+
+    def result(self) -> dict:
+        """{"ap": fp64 [n_class] (NaN for the background and for classes
+        without positives), "map", "npos": int64 [n_class], "n_records",
+        "n_images"}.  Raises ``FrcnnError`` when a batch was dropped because the
+        capacity was too small: the numbers would be of a part of the dataset."""
+        hdr = self.state[0].cpu().numpy()
+        if hdr[2] != 0:
+            raise _lib.FrcnnError(f"VOCEvaluator: {int(hdr[2])} batch(es) did not fit in capacity={self.capacity} "
+                                  f"({int(hdr[0])} records held) and were dropped; use a larger capacity")
+        ap, mean = ops.eval_ap(self.state, int(hdr[0]), use_07_metric=self.use_07_metric)
+        return dict(ap=ap.cpu().numpy(), map=float(mean.item()), npos=hdr[4:].copy(), n_records=int(hdr[0]),
+                    n_images=int(hdr[1]))

@@ -11,6 +11,9 @@
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
   detections for the whole batch (no reference counterpart; DESIGN.md
   "Detections").
+* ``eval_update(...)`` / ``eval_ap(...)`` -- PASCAL VOC evaluation of those
+  detections against ground truth on the device (no reference counterpart:
+  its test_eval.py is empty; DESIGN.md "Evaluation").
 
 Inputs may live on the CPU (reference style); they are moved to the current
 HIP device, and results are returned on the input's device.  Errors follow
@@ -333,6 +336,111 @@ def detect(rois: torch.Tensor, rcount: torch.Tensor, cls: torch.Tensor, reg: tor
                                 _lib.ptr(scores), _lib.ptr(roi), _lib.ptr(count), _lib.ptr(total),
                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "detect")
     return boxes, labels, scores, roi, count, total
+
+
+# ----------------------------------------------------------------- evaluation
+EVAL_MAX_CAPACITY = 1 << 24   # the record index is a 24-bit field of rec_key
+
+
+def eval_state(n_class: int, capacity: int, device=None):
+    """An empty evaluation accumulator (DESIGN.md "Evaluation"): (hdr int64
+    [4 + n_class] zeroed, rec_key int64 [capacity] -- the C-ABI's uint64 keys,
+    whose top bit is never set --, rec_flag int8 [capacity], rec_image int32
+    [capacity]) on the device."""
+    _lib.load()
+    if not 2 <= int(n_class) <= 128 or not 1 <= int(capacity) <= EVAL_MAX_CAPACITY:
+        raise RuntimeError(f"eval_state: n_class={n_class} must be in [2, 128] and capacity={capacity} in "
+                           f"[1, {EVAL_MAX_CAPACITY}]")
+    dev = _lib.device() if device is None else device
+    return (torch.zeros(4 + int(n_class), dtype=torch.int64, device=dev),
+            torch.empty(int(capacity), dtype=torch.int64, device=dev),
+            torch.empty(int(capacity), dtype=torch.int8, device=dev),
+            torch.empty(int(capacity), dtype=torch.int32, device=dev))
+
+
+def _eval_state_check(state, what):
+    want = (torch.int64, torch.int64, torch.int8, torch.int32)
+    if len(state) != 4 or any(not isinstance(t, torch.Tensor) or t.dtype != d or not t.is_cuda or t.dim() != 1
+                              or not t.is_contiguous() for t, d in zip(state, want)):
+        raise RuntimeError(f"{what}: state must be ops.eval_state's (hdr int64, rec_key int64, rec_flag int8, "
+                           "rec_image int32) device tensors")
+    hdr, key, flag, image = state
+    if hdr.numel() < 6 or flag.numel() != key.numel() or image.numel() != key.numel() or key.numel() < 1:
+        raise RuntimeError(f"{what}: state arrays of {hdr.numel()} / {key.numel()} / {flag.numel()} / "
+                           f"{image.numel()} elements do not belong together")
+    return hdr.numel() - 4, key.numel()
+
+
+def eval_update(det, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_difficult: torch.Tensor = None, *,
+                state, iou_thresh: float = 0.5, plus_one: bool = True) -> None:
+    """Score one batch of detections against its ground truth and append the
+    TP / FP / ignored records to ``state`` (frcnn_eval_update; DESIGN.md
+    "Evaluation" is the contract) -- stream-ordered, no allocation, no host
+    synchronisation.
+
+    ``det`` is the tuple ``ops.detect`` returns (or ``(det_boxes, det_labels,
+    det_scores, det_count)``); gt_boxes fp64 [N, G, 4] as [ymin, xmin, ymax,
+    xmax], gt_labels int32 [N, G] (valid rows: 1..n_class-1), gt_difficult
+    uint8 [N, G] or None; all contiguous device tensors.  A batch that does not
+    fit in the state's capacity is dropped as a whole and counted in hdr[2]."""
+    lib = _lib.load()
+    if len(det) == 6:
+        boxes, labels, scores, _, count, _ = det
+    elif len(det) == 4:
+        boxes, labels, scores, count = det
+    else:
+        raise RuntimeError("eval_update: det must be ops.detect's 6-tuple or (boxes, labels, scores, count)")
+    ins = [("det_boxes", boxes, torch.float32), ("det_labels", labels, torch.int32),
+           ("det_scores", scores, torch.float32), ("det_count", count, torch.int32),
+           ("gt_boxes", gt_boxes, torch.float64), ("gt_labels", gt_labels, torch.int32)]
+    if gt_difficult is not None:
+        ins.append(("gt_difficult", gt_difficult, torch.uint8))
+    for name, t, dt in ins:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError(f"eval_update: {name} must be a contiguous {dt} device tensor")
+    C, cap = _eval_state_check(state, "eval_update")
+    if labels.dim() != 2 or gt_labels.dim() != 2:
+        raise RuntimeError("eval_update: det_labels must be [N, M] and gt_labels [N, G]")
+    N, M = labels.shape
+    G = gt_labels.shape[1]
+    if (tuple(boxes.shape) != (N, M, 4) or tuple(scores.shape) != (N, M) or tuple(count.shape) != (N,)
+            or tuple(gt_boxes.shape) != (N, G, 4) or gt_labels.shape[0] != N
+            or (gt_difficult is not None and tuple(gt_difficult.shape) != (N, G))):
+        raise RuntimeError(f"eval_update: det {tuple(boxes.shape)} / {tuple(labels.shape)} / {tuple(scores.shape)} / "
+                           f"{tuple(count.shape)} and gt {tuple(gt_boxes.shape)} / {tuple(gt_labels.shape)} do not "
+                           "match")
+    hdr, key, flag, image = state
+    _lib.check(lib.frcnn_eval_update(N, M, G, C, cap, _lib.ptr(boxes), _lib.ptr(labels), _lib.ptr(scores),
+                                     _lib.ptr(count), _lib.ptr(gt_boxes), _lib.ptr(gt_labels),
+                                     _lib.ptr(gt_difficult), float(iou_thresh), int(bool(plus_one)),
+                                     _lib.ptr(hdr), _lib.ptr(key), _lib.ptr(flag), _lib.ptr(image),
+                                     _lib.stream_ptr()), "eval_update")
+
+
+def eval_ap(state, n_records: int = None, *, use_07_metric: bool = False, return_sorted: bool = False,
+            workspace=None):
+    """Per-class AP and mAP of an accumulator (frcnn_eval_ap): (ap fp64 [C],
+    map fp64 [1]) device tensors, plus the sorted keys (int64 [n_records]) with
+    ``return_sorted``.  ``n_records`` is hdr[0]; when it is not given it is read
+    from the device (a host synchronisation)."""
+    lib = _lib.load()
+    C, cap = _eval_state_check(state, "eval_ap")
+    hdr, key, flag, _ = state
+    n = int(hdr[0].item()) if n_records is None else int(n_records)
+    if not 0 <= n <= cap:
+        raise RuntimeError(f"eval_ap: n_records={n} outside the state's capacity {cap}")
+    dev = hdr.device
+    ap = torch.empty(C, dtype=torch.float64, device=dev)
+    mean = torch.empty(1, dtype=torch.float64, device=dev)
+    skey = torch.empty(n, dtype=torch.int64, device=dev) if return_sorted else None
+    need = int(lib.frcnn_eval_ap_workspace_size(C, max(n, 1)))
+    ws = workspace if workspace is not None else _lib.cached_workspace("eval_ap", need, dev)
+    if ws.numel() < need:
+        raise RuntimeError(f"eval_ap: workspace of {ws.numel()} B < {need} B")
+    _lib.check(lib.frcnn_eval_ap(C, n, _lib.ptr(hdr), _lib.ptr(key), _lib.ptr(flag), int(bool(use_07_metric)),
+                                 _lib.ptr(ap), _lib.ptr(mean), _lib.ptr(skey) if n else None, _lib.ptr(ws),
+                                 ws.numel(), _lib.stream_ptr()), "eval_ap")
+    return (ap, mean, skey) if return_sorted else (ap, mean)
 
 
 # ------------------------------------------------------------- RPN epilogue
