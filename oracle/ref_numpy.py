@@ -3,12 +3,14 @@
 numpy restatement of the reference hot path.  Every function cites the
 reference file:line it follows.  Arithmetic types follow the reference
 exactly (fp32 where the reference computes in fp32 torch/numpy, fp64 where it
-computes in fp64 numpy), with one documented deviation:
+computes in fp64 numpy), with these documented deviations:
 
 * ``exp`` in the box decode is correctly rounded (fp64 exp, then rounded to
   fp32).  The reference calls torch CPU ``exp`` (MKL VML), whose last bit
   depends on the host ISA path (SURVEY.md §7 "Host-dependent exp"), so decoded
   boxes are held to the 1e-5 relative contract and kept indices bit-exact.
+* ``log`` in ``bbox2reg`` with both inputs fp32 is correctly rounded in the
+  same way (``log_cr``); the other dtype combinations compute in fp64.
 * ``argsort`` of the proposal scores is stable (ties by ascending post-filter
   position).  The reference's torch CPU argsort is unstable under ties; parity
   inputs are tie-free.
@@ -129,6 +131,16 @@ def rpn_head_epilogue(cls, reg):
     return c, (e1 * inv).astype(np.float32), r                                # :119-120
 
 
+def log_cr(v):
+    """log in the dtype of ``v``; for fp32 correctly rounded (fp64 log, rounded
+    once to fp32) -- numpy's fp32 log is a host SIMD routine whose last bit
+    depends on the machine, like exp (module docstring)."""
+    v = np.asarray(v)
+    if v.dtype == np.float32:
+        return np.log(v.astype(np.float64)).astype(np.float32)
+    return np.log(v)
+
+
 def bbox2reg(anchors, bbox):
     """utils/utils.py:75-100.  Anchor statistics in the anchors' dtype, box
     statistics in the boxes' dtype, output fp64."""
@@ -143,8 +155,8 @@ def bbox2reg(anchors, bbox):
     out = np.zeros(bbox.shape)
     out[:, 0] = (bcx - acx) / ah
     out[:, 1] = (bcy - acy) / aw
-    out[:, 2] = np.log(bh / ah)
-    out[:, 3] = np.log(bw / aw)
+    out[:, 2] = log_cr(bh / ah)
+    out[:, 3] = log_cr(bw / aw)
     return out
 
 

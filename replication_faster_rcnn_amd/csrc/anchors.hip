@@ -77,10 +77,10 @@ extern "C" int frcnn_anchor_base(const double* ratios, int n_ratios, const doubl
 
 extern "C" int frcnn_generate_anchors(const float* anchor_base, int K, int feat_stride, int width,
                                       int height, float* out, void* stream) {
-    FRCNN_REQUIRE(anchor_base && out, "frcnn_generate_anchors: null pointer");
     FRCNN_REQUIRE(K > 0 && width >= 0 && height >= 0, "frcnn_generate_anchors: bad shape");
     int64_t total = static_cast<int64_t>(K) * width * height;
-    if (total == 0) return FRCNN_OK;
+    if (total == 0) return FRCNN_OK;  // an empty grid: the empty output has no address
+    FRCNN_REQUIRE(anchor_base && out, "frcnn_generate_anchors: null pointer");
     unsigned blocks = static_cast<unsigned>((total + 255) / 256);
     hipLaunchKernelGGL(generate_anchors_kernel, dim3(blocks), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const float4*>(anchor_base), K, feat_stride, width, total,

@@ -107,13 +107,18 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
     return l == 0 ? 0ull : (~0ull >> (64 - l));
 }
 
-// Order-preserving map of an fp32 score to a u32 that sorts ASCENDING for
-// DESCENDING scores (NaN first, like torch's descending sort).
+// Map of an fp32 score to a u32 that sorts ASCENDING for DESCENDING scores,
+// with the equalities of torch's descending sort: every NaN (either sign, any
+// payload) gets the one smallest key 0, so NaNs come first and the index
+// decides among them; -0.0 gets +0.0's key.  Keys of non-NaN scores lie in
+// [0x007FFFFF (+inf), 0xFF800000 (-inf)], so 0xFFFFFFFF, which the callers
+// reserve for "invalid", is never produced.
 __device__ __forceinline__ uint32_t desc_score_key(float s) {
+    if (s != s) return 0u;
     uint32_t u = __float_as_uint(s);
+    if (u == 0x80000000u) u = 0u;
     uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    uint32_t k = ~asc;
-    return k == 0xFFFFFFFFu ? 0xFFFFFFFEu : k;  // 0xFFFFFFFF is reserved for "invalid"
+    return ~asc;
 }
 
 // torch.clamp(v, lo, hi) on fp32 with NaN propagation (nets/rpn.py:62-63).

@@ -1830,7 +1830,10 @@ __global__ __launch_bounds__(256) void bbox_iou_kernel(const TA* __restrict__ a,
 }
 
 // utils/utils.py:75-100 with numpy promotion: anchor statistics in the
-// anchors' dtype, box statistics in the boxes' dtype, result fp64.
+// anchors' dtype, box statistics in the boxes' dtype, result fp64.  With both
+// fp32 numpy takes its fp32 log, a host SIMD routine whose last bit depends on
+// the machine: like exp_cr the log is taken in fp64 and rounded once to fp32
+// (SURVEY.md §7 "Host-dependent exp"), never logf.
 template <class TA, class TB>
 __global__ __launch_bounds__(256) void bbox2reg_kernel(const TA* __restrict__ a,
                                                        const TB* __restrict__ b, int64_t n,
@@ -1847,8 +1850,8 @@ __global__ __launch_bounds__(256) void bbox2reg_kernel(const TA* __restrict__ a,
     if (sizeof(TA) == 4 && sizeof(TB) == 4) {  // both fp32: numpy computes in fp32, stores fp64
         o[0] = static_cast<double>((bcx - acx) / ah);
         o[1] = static_cast<double>((bcy - acy) / aw);
-        o[2] = static_cast<double>(logf(static_cast<float>(bh / ah)));
-        o[3] = static_cast<double>(logf(static_cast<float>(bw / aw)));
+        o[2] = static_cast<double>(static_cast<float>(log(static_cast<double>(bh / ah))));
+        o[3] = static_cast<double>(static_cast<float>(log(static_cast<double>(bw / aw))));
     } else {
         o[0] = (static_cast<double>(bcx) - static_cast<double>(acx)) / static_cast<double>(ah);
         o[1] = (static_cast<double>(bcy) - static_cast<double>(acy)) / static_cast<double>(aw);

@@ -15,9 +15,19 @@
   detections against ground truth on the device (no reference counterpart:
   its test_eval.py is empty; DESIGN.md "Evaluation").
 
-Inputs may live on the CPU (reference style); they are moved to the current
-HIP device, and results are returned on the input's device.  Errors follow
-torchvision's ``TORCH_CHECK`` -> ``RuntimeError`` convention.
+Two input rules (tests/test_gpu_wrapper_inputs.py):
+
+* The reference-signature drop-ins (``nms``, ``roi_pool*``, ``roi_pool_head``,
+  ``rpn_head_epilogue``) convert whatever they are given: inputs may live on the
+  CPU (reference style), be strided views or another float type; they are moved
+  to the current HIP device as contiguous fp32, and results are returned on the
+  input's device.  They raise only on shapes that do not belong together.
+* The hot-path ops on device tensors (``propose``, ``roi_transform``,
+  ``detect``, ``eval_update``) convert nothing: every tensor must already be a
+  contiguous device tensor of the documented dtype and exact shape, checked by
+  attribute reads alone (no copy, no synchronisation) before any launch.
+
+Errors follow torchvision's ``TORCH_CHECK`` -> ``RuntimeError`` convention.
 """
 from __future__ import annotations
 
@@ -33,6 +43,17 @@ def _to_dev(t: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     if t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.device.index == _lib._cur_device():
         return t
     return t.to(device=_lib.device(), dtype=dtype).contiguous()
+
+
+def _require(op: str, name: str, t, dtype, shape) -> None:
+    """The hot-path ops' input rule: ``t`` is a contiguous device tensor of
+    ``dtype`` and exactly ``shape``.  Attribute reads only."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()
+            or t.shape != shape):
+        got = (f"{'contiguous' if t.is_contiguous() else 'strided'} {t.dtype} {t.device.type} tensor of shape "
+               f"{list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__)
+        raise RuntimeError(f"{op}: {name} must be a contiguous {dtype} device tensor of shape {list(shape)}; "
+                           f"got a {got}")
 
 
 # ----------------------------------------------------------------------- nms
@@ -228,11 +249,28 @@ def propose(scores: torch.Tensor, deltas: torch.Tensor, *, img_w: float, img_h: 
     [A, 4] or ``anchor_base`` [K, 4] + the feature grid (anchors generated in
     the decode kernel).  Returns padded (rois [N, post, 4], anchor_idx int32
     [N, post], count int32 [N]) -- no host synchronisation.
+
+    A hot-path op: nothing is converted.  ``scores``, ``deltas``, ``anchors``,
+    ``anchor_base`` and the ``out`` buffers must be contiguous device tensors of
+    the dtypes and exact shapes above (RuntimeError naming the argument
+    otherwise; attribute reads only, before any launch).  A strided view such
+    as ``softmax(cls, -1)[..., 1]`` needs ``.contiguous()`` first.
     """
     lib = _lib.load()
-    dev = scores.device
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+        raise RuntimeError("propose: scores must be a contiguous torch.float32 device tensor of shape [N, A]")
     N, A = scores.shape
-    K = 0 if anchors is None and anchor_base is None else (anchor_base.size(0) if anchors is None else 0)
+    _require("propose", "scores", scores, torch.float32, (N, A))
+    _require("propose", "deltas", deltas, torch.float32, (N, A, 4))
+    dev = scores.device
+    if anchors is not None:
+        K = 0
+        _require("propose", "anchors", anchors, torch.float32, (A, 4))
+    elif anchor_base is not None:
+        K = anchor_base.size(0) if isinstance(anchor_base, torch.Tensor) and anchor_base.dim() == 2 else -1
+        _require("propose", "anchor_base", anchor_base, torch.float32, (K, 4))
+    else:
+        raise RuntimeError("propose: give anchors [A, 4] or anchor_base [K, 4] with the feature grid")
     key = (N, A, K, feat_h, feat_w, feat_stride, float(img_h), float(img_w), float(min_size),
            int(pre_nms), int(post_nms), float(nms_thresh))
     cached = _params_cache.get(key)
@@ -252,14 +290,16 @@ def propose(scores: torch.Tensor, deltas: torch.Tensor, *, img_w: float, img_h: 
         idx = torch.empty((N, post_nms), dtype=torch.int32, device=dev)
         cnt = torch.empty((N,), dtype=torch.int32, device=dev)
     else:  # caller-owned outputs (static buffers of a captured HIP graph)
-        rois, idx, cnt = out
-        if (tuple(rois.shape) != (N, post_nms, 4) or tuple(idx.shape) != (N, post_nms)
-                or tuple(cnt.shape) != (N,) or rois.dtype != torch.float32
-                or idx.dtype != torch.int32 or cnt.dtype != torch.int32):
+        if len(out) != 3:
             raise RuntimeError("propose: out buffers must be fp32 [N,post,4], int32 [N,post], int32 [N]")
+        rois, idx, cnt = out
+        _require("propose", "out[0] (rois)", rois, torch.float32, (N, post_nms, 4))
+        _require("propose", "out[1] (anchor_idx)", idx, torch.int32, (N, post_nms))
+        _require("propose", "out[2] (count)", cnt, torch.int32, (N,))
     ws = workspace if workspace is not None else _lib.cached_workspace("propose", need, dev)
-    if ws.numel() < need:
-        raise RuntimeError(f"propose: workspace of {ws.numel()} B < {need} B")
+    if not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError(f"propose: workspace must be a contiguous uint8 device tensor of at least {need} B; "
+                           f"got {ws.dtype} on {ws.device.type} with {ws.numel()} elements")
     _lib.check(lib.frcnn_propose(p, _lib.ptr(scores), _lib.ptr(deltas), _lib.ptr(anchors),
                                  _lib.ptr(anchor_base), _lib.ptr(rois), _lib.ptr(idx),
                                  _lib.ptr(cnt), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
@@ -490,9 +530,16 @@ def rpn_head_epilogue(cls: torch.Tensor, reg: torch.Tensor, K: int):
 
 def roi_transform(rois: torch.Tensor, roi_inds: torch.Tensor, img_h, img_w, feat_h: int,
                   feat_w: int) -> torch.Tensor:
-    """nets/heads.py:42-47 on device: [R,4] image rois + [R] inds -> [R,5]."""
+    """nets/heads.py:42-47 on device: fp32 [R,4] image rois + fp32 [R] inds ->
+    fp32 [R,5].  A hot-path op: ``rois`` and ``roi_inds`` must be contiguous fp32
+    device tensors of these shapes (RuntimeError naming the argument otherwise;
+    attribute reads only, before any launch)."""
     lib = _lib.load()
+    if not isinstance(rois, torch.Tensor) or rois.dim() != 2:
+        raise RuntimeError("roi_transform: rois must be a contiguous torch.float32 device tensor of shape [R, 4]")
     R = rois.size(0)
+    _require("roi_transform", "rois", rois, torch.float32, (R, 4))
+    _require("roi_transform", "roi_inds", roi_inds, torch.float32, (R,))
     out = torch.empty((R, 5), dtype=torch.float32, device=rois.device)
     _lib.check(lib.frcnn_roi_transform(_lib.ptr(rois), _lib.ptr(roi_inds), R, float(img_h),
                                        float(img_w), int(feat_h), int(feat_w), _lib.ptr(out),

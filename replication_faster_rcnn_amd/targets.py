@@ -8,6 +8,15 @@ by shipping the MT19937 state to the device and back (one round trip per
 call -- the only host synchronisation).  A caller that owns a device-resident
 RNG stream (``rng=``: int32 [625] from ``utils.rng_state_to_device``) skips the
 round trip: the state advances in place on the device, sync-free.
+
+Input rule (tests/test_gpu_wrapper_inputs.py): these are reference-signature
+drop-ins, so ``boxes``, ``labels``, ``anchors``, ``rois`` and ``rcount`` are
+converted from whatever they are (numpy or tensor, any device, any float type,
+strided views) to contiguous device tensors of the kernels' types.  What is
+not converted is checked: shapes that do not belong together (``rois`` /
+``rcount`` / ``boxes`` disagreeing on N, ``anchors`` not [A, 4]) and caller-owned
+``out=`` buffers of another shape, dtype or layout raise RuntimeError before
+any launch.
 """
 from __future__ import annotations
 
@@ -28,6 +37,32 @@ def _gt(boxes, labels, dev):
     return b, l
 
 
+def _anchors(anchors, dev):
+    a = anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.asarray(anchors, np.float32))
+    if a.dim() != 2 or a.size(1) != 4:
+        raise RuntimeError(f"anchors must be [A,4]; got {tuple(a.shape)}")
+    return a.to(dev, torch.float32).contiguous()
+
+
+def _rois(rois, rcount, N, dev):
+    r = rois if isinstance(rois, torch.Tensor) else torch.as_tensor(np.asarray(rois))
+    c = rcount if isinstance(rcount, torch.Tensor) else torch.as_tensor(np.asarray(rcount))
+    if r.dim() != 3 or r.size(2) != 4 or r.size(0) != N or tuple(c.shape) != (N,):
+        raise RuntimeError(f"rois must be [N,Rp,4] and rcount [N] for the N={N} images of boxes; got "
+                           f"{tuple(r.shape)}, {tuple(c.shape)}")
+    return r.to(dev, torch.float32).contiguous(), c.to(dev, torch.int32).contiguous()
+
+
+def _check_out(what, out, want, dev):
+    """Caller-owned output buffers: contiguous tensors on the plan's device of
+    exactly the (shape, dtype) the kernels write."""
+    if len(out) != len(want) or any(
+            not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.dtype != d or t.device != dev
+            or not t.is_contiguous() for t, (s, d) in zip(out, want)):
+        raise RuntimeError(f"{what}: out buffers must be contiguous device tensors "
+                           + ", ".join(f"{str(d).replace('torch.', '')} {list(s)}" for s, d in want))
+
+
 def anchor_targets(boxes, labels, anchors, n_sample=256, pos_iou_thresh=0.7, neg_iou_thresh=0.3,
                    pos_ratio=0.5, sample=True, internals=False, rng=None):
     """boxes [N,G,4] fp64 (label -1 rows = padding), labels [N,G], anchors [A,4]
@@ -37,8 +72,7 @@ def anchor_targets(boxes, labels, anchors, n_sample=256, pos_iou_thresh=0.7, neg
     lib = _lib.load()
     dev = _lib.device()
     b, l = _gt(boxes, labels, dev)
-    a = (anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.asarray(anchors, np.float32)))
-    a = a.to(dev, torch.float32).contiguous()
+    a = _anchors(anchors, dev)
     N, G = b.shape[:2]
     A = a.size(0)
     reg = torch.empty((N, A, 4), dtype=torch.float64, device=dev)
@@ -87,8 +121,7 @@ def anchor_targets_prepare(boxes, labels, anchors, pos_iou_thresh=0.7, neg_iou_t
     lib = _lib.load()
     dev = _lib.device()
     b, l = _gt(boxes, labels, dev)
-    a = (anchors if isinstance(anchors, torch.Tensor) else torch.as_tensor(np.asarray(anchors, np.float32)))
-    a = a.to(dev, torch.float32).contiguous()
+    a = _anchors(anchors, dev)
     N, G = b.shape[:2]
     A = a.size(0)
     ws = workspace if workspace is not None else anchor_targets_workspace(N, A, G, dev)
@@ -110,6 +143,7 @@ def anchor_targets_sample(plan, n_sample=256, pos_ratio=0.5, rng=None, out=None)
         reg = torch.empty((N, A, 4), dtype=torch.float64, device=dev)
         lab = torch.empty((N, A), dtype=torch.int32, device=dev)
     else:
+        _check_out("anchor_targets_sample", out, [((N, A, 4), torch.float64), ((N, A), torch.int32)], dev)
         reg, lab = out
     own = rng is None
     if own:
@@ -167,6 +201,8 @@ def anchor_targets_finish(plan, out=None):
     if out is None:
         out = (torch.empty((N, A, 4), dtype=torch.float64, device=dev),
                torch.empty((N, A), dtype=torch.int32, device=dev))
+    else:
+        _check_out("anchor_targets_finish", out, [((N, A, 4), torch.float64), ((N, A), torch.int32)], dev)
     reg, lab = out
     _lib.check(lib.frcnn_anchor_target_finish(N, A, plan.G, _lib.ptr(plan.anchors), _lib.ptr(reg), _lib.ptr(lab),
                                               None, None, _lib.ptr(plan.ws), plan.ws.numel(), _lib.stream_ptr()),
@@ -183,9 +219,8 @@ def proposal_targets(rois, rcount, boxes, labels, n_sample=128, pos_ratio=0.5, p
     lib = _lib.load()
     dev = _lib.device()
     b, l = _gt(boxes, labels, dev)
-    r = rois.to(dev, torch.float32).contiguous()
-    c = rcount.to(dev, torch.int32).contiguous()
     N, G = b.shape[:2]
+    r, c = _rois(rois, rcount, N, dev)
     Rp = r.size(1)
     s_roi = torch.empty((N, n_sample, 4), dtype=torch.float64, device=dev)
     s_reg = torch.empty((N, n_sample, 4), dtype=torch.float64, device=dev)
@@ -234,9 +269,8 @@ def proposal_targets_prepare(rois, rcount, boxes, labels, n_sample=128, pos_iou_
     lib = _lib.load()
     dev = _lib.device()
     b, l = _gt(boxes, labels, dev)
-    r = rois.to(dev, torch.float32).contiguous()
-    c = rcount.to(dev, torch.int32).contiguous()
     N, G = b.shape[:2]
+    r, c = _rois(rois, rcount, N, dev)
     Rp = r.size(1)
     ws = workspace if workspace is not None else proposal_targets_workspace(N, Rp, G, n_sample, dev)
     _lib.check(lib.frcnn_proposal_target_prepare(N, Rp, _lib.ptr(r), _lib.ptr(c), G, _lib.ptr(b), _lib.ptr(l),
@@ -261,6 +295,9 @@ def proposal_targets_sample(plan, pos_ratio=0.5, reg_normalize_mean=(0., 0., 0.,
                torch.empty((N, S, 4), dtype=torch.float64, device=dev),
                torch.empty((N, S), dtype=torch.float64, device=dev),
                torch.empty((N,), dtype=torch.int32, device=dev))
+    else:
+        _check_out("proposal_targets_sample", out, [((N, S, 4), torch.float64), ((N, S, 4), torch.float64),
+                                                    ((N, S), torch.float64), ((N,), torch.int32)], dev)
     s_roi, s_reg, s_lab, s_cnt = out
     mean = np.asarray(reg_normalize_mean, np.float32).astype(np.float64)  # utils/utils.py:272
     std = np.asarray(reg_normalize_std, np.float32).astype(np.float64)
@@ -332,6 +369,12 @@ def proposal_targets_finish(plan, count, reg_normalize_mean=(0., 0., 0., 0.),
         out = (torch.empty((N, S, 4), dtype=torch.float64, device=dev),
                torch.empty((N, S, 4), dtype=torch.float64, device=dev),
                torch.empty((N, S), dtype=torch.float64, device=dev))
+    else:
+        _check_out("proposal_targets_finish", out, [((N, S, 4), torch.float64), ((N, S, 4), torch.float64),
+                                                    ((N, S), torch.float64)], dev)
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (N,) \
+            or count.device != dev or not count.is_contiguous():
+        raise RuntimeError("proposal_targets_finish: count must be proposal_targets_draw's int32 [N] device tensor")
     s_roi, s_reg, s_lab = out
     mean = np.asarray(reg_normalize_mean, np.float32).astype(np.float64)  # utils/utils.py:272
     std = np.asarray(reg_normalize_std, np.float32).astype(np.float64)

@@ -1,6 +1,11 @@
 """Box utilities and target creators (utils/utils.py) on the HIP path.
 
 Module constants and signatures mirror utils/utils.py:6-21 and :47-276.
+
+Input rule: these are reference-signature drop-ins, so numpy arrays, CPU or
+device tensors, strided views and other float types are converted to
+contiguous device tensors of the kernels' types; shapes that do not belong
+together raise (RuntimeError; bbox_iou's IndexError is the reference's own).
 """
 from __future__ import annotations
 
@@ -99,6 +104,8 @@ def bbox2reg(anchors, bbox):
     b64 = _np_dtype_of(bbox) != np.float32
     dev = _lib.device()
     ta, tb = _as_dev(anchors, a64, dev), _as_dev(bbox, b64, dev)
+    if ta.shape != tb.shape or ta.dim() != 2 or ta.size(1) != 4:
+        raise RuntimeError(f"bbox2reg: anchors {tuple(ta.shape)} and bbox {tuple(tb.shape)} must both be [n, 4]")
     out = torch.empty((tb.size(0), 4), device=dev, dtype=torch.float64)
     _lib.check(lib.frcnn_bbox2reg(_lib.ptr(ta), int(a64), _lib.ptr(tb), int(b64), tb.size(0),
                                   _lib.ptr(out), _lib.stream_ptr()), "bbox2reg")

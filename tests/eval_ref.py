@@ -15,11 +15,20 @@ GARBAGE_BOX, GARBAGE_LABEL, GARBAGE_SCORE = 1e30, 1, 9.0   # slots at or past th
 
 
 def desc_score_key(s):
-    """csrc/common.h desc_score_key: fp32 -> uint32 ascending for descending scores."""
-    u = np.ascontiguousarray(s, np.float32).view(np.uint32)
+    """csrc/common.h desc_score_key: fp32 -> uint32 ascending for descending scores,
+    with torch's equalities: every NaN gets key 0, -0.0 gets +0.0's key."""
+    s = np.ascontiguousarray(s, np.float32)
+    u = np.where(s == 0, np.float32(0), s).view(np.uint32)
     asc = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
-    k = ~asc
-    return np.where(k == np.uint32(0xFFFFFFFF), np.uint32(0xFFFFFFFE), k).astype(np.uint32)
+    return np.where(np.isnan(s), np.uint32(0), ~asc).astype(np.uint32)
+
+
+def desc_order(s):
+    """Slots in torch's own stable descending order (NaN first, -0.0 == +0.0,
+    ties by slot): the order the devkit loop walks an image's detections in."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(s, np.float32))
+    return torch.sort(t, descending=True, stable=True).indices.numpy().tolist()
 
 
 def iou(a, b, plus_one=1):
@@ -47,8 +56,7 @@ def match_image(boxes, labels, scores, k, gt_boxes, gt_labels, gt_difficult, C, 
     cls = np.zeros(k, np.int64)
     best = np.full(k, -1, np.int64)
     taken = np.zeros(len(gt_labels), bool)
-    keys = desc_score_key(scores[:k])
-    for s in sorted(range(k), key=lambda i: (int(keys[i]), i)):
+    for s in desc_order(scores[:k]):
         lab = int(labels[s])
         if not 1 <= lab < C:
             flag[s] = -1

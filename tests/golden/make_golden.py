@@ -10,6 +10,12 @@ tests/target_cases.py through the genuine creators):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py target_edges
 
+or, for tests/golden/box_utils_edges.npz alone (the case table of
+tests/box_cases.py through the genuine box utilities, anchors and the head's
+RoI transform):
+
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py box_edges
+
 The reference modules utils/anchors.py, utils/utils.py, nets/rpn.py and
 nets/heads.py are imported read-only (no bytecode is written) with
 tests/golden/_tvstub standing in for torchvision, which the reference imports
@@ -342,9 +348,91 @@ def gen_roi_pool():
          boxes=boxes, out=out, argmax=am, grad=g, grad_in=gi)
 
 
+# ---------------------------------------------------------------------------
+class _Captured(Exception):
+    pass
+
+
+def _ref_roi_transform(rois, inds, img_h, img_w, feat_h, feat_w):
+    """nets/heads.py:42-47 by the genuine ResnetHead.forward: its roi_pool is
+    replaced by a recorder that stops the forward once the boxes exist (no
+    pooling arithmetic on NaN / infinite boxes)."""
+    got = []
+
+    def recorder(x, boxes, output_size, spatial_scale):
+        got.append(boxes.detach().numpy().copy())
+        raise _Captured
+
+    head = ref_heads.ResnetHead(torch.nn.Identity())
+    saved = ref_heads.roi_pool
+    ref_heads.roi_pool = recorder
+    try:
+        with torch.no_grad():
+            head(torch.zeros(1, 1, feat_h, feat_w), torch.from_numpy(rois), torch.from_numpy(inds), img_h, img_w)
+    except _Captured:
+        pass
+    finally:
+        ref_heads.roi_pool = saved
+    (boxes,) = got
+    return boxes
+
+
+def gen_box_edges():
+    """tests/box_cases.py through the genuine utils/utils.py, utils/anchors.py and
+    nets/heads.py:42-47.  Inputs that the table rebuilds exactly (every value is
+    exact in fp32) are stored once, as fp32; bbox2reg is elementwise, so the
+    n = 257 outputs are stored and the smaller sizes asserted to be their
+    prefixes, here, on the genuine function."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import warnings
+    import box_cases as bc
+    res = {}
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        for name, (a, b) in bc.iou_cases().items():
+            out = ref_utils.bbox_iou(a, b)
+            res[name + "__a"], res[name + "__b"] = a.astype(np.float32) if a.dtype.kind == "f" else a, \
+                b.astype(np.float32) if b.dtype.kind == "f" else b
+            res[name + "__out"] = out
+        a64, b64 = bc.b2r_table()
+        res["b2r__anchors"], res["b2r__boxes"] = a64.astype(np.float32), b64.astype(np.float32)
+        for ta, tb in bc.DTYPES:
+            full = ref_utils.bbox2reg(a64.astype(ta), b64.astype(tb))
+            assert full.dtype == np.float64
+            for n in bc.B2R_SIZES:
+                part = ref_utils.bbox2reg(a64[:n].astype(ta), b64[:n].astype(tb))
+                assert part.dtype == np.float64 and np.array_equal(part, full[:n], equal_nan=True), (ta, tb, n)
+            res[f"b2r_257_{bc.tag(ta, tb)}__out"] = full
+        anc, dl = bc.r2b_table()
+        res["r2b__anchors"], res["r2b__deltas"] = anc, dl
+        for n in bc.R2B_SIZES:
+            out = ref_utils.reg2bbox(torch.from_numpy(anc[:n]), torch.from_numpy(dl[:n])).numpy()
+            assert out.dtype == np.float32
+            res[f"r2b_{n}__out"] = out
+        rois, inds = bc.roi_table()
+        res["roi__rois"], res["roi__inds"] = rois, inds
+        for n in bc.ROI_SIZES:
+            res[f"roi_{n}__boxes"] = _ref_roi_transform(rois[:n], inds[:n], bc.ROI_IMG_H, bc.ROI_IMG_W,
+                                                        bc.ROI_FEAT_H, bc.ROI_FEAT_W)
+        for name, (base_size, ratios, scales) in bc.BASE_CASES.items():
+            res[f"base_{name}"] = ref_anchors.generate_anchor_base(base_size, list(ratios), list(scales))
+        for name, (bname, stride, w, h) in bc.GRID_CASES.items():
+            a = ref_anchors.generate_anchors(res[f"base_{bname}"], stride, w, h)
+            assert a.dtype == np.float32
+            res[f"grid_{name}__shape"] = np.array(a.shape)
+            res[f"grid_{name}__sha"] = np.array(sha(a))
+            if a.size <= 400:
+                res[f"grid_{name}"] = a
+    save("box_utils_edges.npz", **res)
+    assert os.path.getsize(os.path.join(HERE, "box_utils_edges.npz")) < 100 * 1024
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["target_edges"]:
         gen_target_edges()
+        sys.exit(0)
+    if sys.argv[1:] == ["box_edges"]:
+        gen_box_edges()
         sys.exit(0)
     gen_anchors()
     gen_reg2bbox()
@@ -353,3 +441,4 @@ if __name__ == "__main__":
     gen_proposals()
     gen_targets()
     gen_target_edges()
+    gen_box_edges()

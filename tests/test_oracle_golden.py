@@ -177,3 +177,152 @@ def test_rpn_head_epilogue_oracle_vs_torch(K, H, W):
     c, fg, r = orc.rpn_head_epilogue(cls.numpy(), reg.numpy())
     assert np.array_equal(c, c_t.numpy()) and np.array_equal(r, r_t.numpy())
     np.testing.assert_allclose(fg, fg_t.numpy(), rtol=1e-6, atol=1e-30)
+
+
+# ---------------------------------------------------------------------------
+# box-utility edge table (tests/box_cases.py) against box_utils_edges.npz
+import box_cases as bc  # noqa: E402
+
+# The largest distance, in fp32 ulps, between numpy's fp32 log (what the golden
+# holds for the both-fp32 bbox2reg) and the correctly rounded log (what the
+# oracle and the kernel compute), measured over the table's finite log
+# arguments on the host that wrote the golden.
+LOG_F32_ULPS = 2
+
+
+def ulp_distance_f32(a, b):
+    """Distance in fp32 ulps of two finite fp32 arrays of equal sign pattern."""
+    a = np.ascontiguousarray(a, np.float32).view(np.int32).astype(np.int64)
+    b = np.ascontiguousarray(b, np.float32).view(np.int32).astype(np.int64)
+    return np.abs(a - b)
+
+
+@pytest.mark.parametrize("name", list(bc.iou_cases()))
+def test_box_edges_iou(golden, name):
+    g = golden("box_utils_edges.npz")
+    a, b = bc.iou_cases()[name]
+    assert np.array_equal(a.astype(np.float64), g[name + "__a"].astype(np.float64), equal_nan=True)
+    assert np.array_equal(b.astype(np.float64), g[name + "__b"].astype(np.float64), equal_nan=True)
+    with np.errstate(all="ignore"):
+        out = orc.bbox_iou(a, b)
+    ref = g[name + "__out"]
+    assert out.dtype == ref.dtype and out.shape == ref.shape == (len(a), len(b))
+    np.testing.assert_array_equal(out, ref)     # NaN positions equal
+
+
+def test_box_edges_iou_preconditions():
+    """The rows do what the table says, on the oracle alone."""
+    c = bc.iou_cases()
+    with np.errstate(all="ignore"):
+        assert np.isnan(orc.bbox_iou(*c["iou_1x1_f64_f64"])).all()          # 0 / 0
+        a, b = c["iou_255x3_f64_f64"]
+        o64 = orc.bbox_iou(a, b)
+        o32 = orc.bbox_iou(*c["iou_255x3_f32_f32"])
+        s = orc.bbox_iou(bc.IOU_SPECIAL, bc.IOU_SPECIAL)
+    assert o32.dtype == np.float32 and o64.dtype == np.float64
+    assert s[1, 2] == 0 and s[2, 1] == 0                                     # touching: tl == br
+    assert s[1, 1] == 1 and s[11, 1] > 0
+    assert np.isnan(s[0, 0]) and (s[3, [1, 2, 11]] == 0).all()               # inverted: never tl < br
+    assert np.isnan(s[4, 1]) and np.isnan(s[1, 4]) and np.isnan(s[4, 4]) and not np.isnan(s[1, 1])
+    nan_a, nan_b = np.isnan(a).any(1), np.isnan(b).any(1)
+    assert nan_a.any() and not nan_a.all() and nan_b.any() and not nan_b.all()   # a only, b only, both, neither
+    assert np.isnan(o64[nan_a][:, nan_b]).all()
+    big = np.nonzero((a == bc.BIG).any(1))[0][0]
+    assert o64[big, 2] > 0 and o32[big, 2] == 0                              # 1e20: the fp32 area overflows to inf
+    with np.errstate(all="ignore"):
+        s32 = orc.bbox_iou(bc.IOU_SPECIAL.astype(np.float32), bc.IOU_SPECIAL.astype(np.float32))
+    assert s[9, 10] == 0.25 and np.isnan(s32[9, 10])                         # ... and inf / (inf + inf - inf)
+    assert np.isinf(a).any()
+
+
+@pytest.mark.parametrize("name", list(bc.b2r_cases()))
+def test_box_edges_bbox2reg(golden, name):
+    g = golden("box_utils_edges.npz")
+    a, b = bc.b2r_cases()[name]
+    n = len(a)
+    assert np.array_equal(a, g["b2r__anchors"][:n].astype(a.dtype), equal_nan=True)
+    assert np.array_equal(b, g["b2r__boxes"][:n].astype(b.dtype), equal_nan=True)
+    ref = g["b2r_257_" + name.split("_", 2)[2] + "__out"][:n]
+    with np.errstate(all="ignore"):
+        out = orc.bbox2reg(a, b)
+    assert out.dtype == np.float64 and out.shape == (n, 4)
+    np.testing.assert_array_equal(out[:, :2], ref[:, :2])
+    fin = np.isfinite(ref[:, 2:])
+    np.testing.assert_array_equal(out[:, 2:][~fin], ref[:, 2:][~fin])        # -inf, +inf and NaN in place
+    if name.endswith("f32_f32"):
+        d = ulp_distance_f32(out[:, 2:][fin], ref[:, 2:][fin])
+        print(name, "largest distance to numpy's fp32 log:", int(d.max()) if d.size else 0, "ulp")
+        assert (d <= LOG_F32_ULPS).all()
+    else:
+        np.testing.assert_allclose(out[:, 2:][fin], ref[:, 2:][fin], rtol=1e-12, atol=0)
+
+
+def test_box_edges_bbox2reg_preconditions(golden):
+    a, b = bc.b2r_table()
+    with np.errstate(all="ignore"):
+        o = orc.bbox2reg(a, b)
+    assert np.isfinite(o[0]).all()                                           # the n = 1 case is a plain pair
+    assert np.isposinf(o[2, 2]) and np.isneginf(o[3, 2]) and np.isnan(o[4, 2]) and np.isnan(o[5]).any()
+    assert np.isnan(o[7, 2]) and (o[8] == 0).all()
+    # the margin above is the measured one
+    x = bc.b2r_log_arguments()
+    x = x[np.isfinite(x) & (x > 0)]
+    ref = golden("box_utils_edges.npz")["b2r_257_f32_f32__out"][:, 2:].T.ravel()
+    ref = ref[np.isfinite(ref)]
+    assert len(ref) == len(x) > 400
+    d = ulp_distance_f32(orc.log_cr(x), ref)
+    assert d.max() == LOG_F32_ULPS
+
+
+@pytest.mark.parametrize("n", bc.R2B_SIZES)
+def test_box_edges_reg2bbox(golden, n):
+    g = golden("box_utils_edges.npz")
+    anc, dl = bc.r2b_table()
+    assert np.array_equal(anc, g["r2b__anchors"]) and np.array_equal(dl, g["r2b__deltas"], equal_nan=True)
+    with np.errstate(all="ignore"):
+        out = orc.reg2bbox(anc[:n], dl[:n])
+    ref = g[f"r2b_{n}__out"]
+    assert out.dtype == ref.dtype == np.float32 and out.shape == ref.shape == (n, 4)
+    fin = np.isfinite(ref)
+    np.testing.assert_array_equal(out[~fin], ref[~fin])                      # +-inf and NaN in place
+    np.testing.assert_allclose(out[fin], ref[fin], rtol=1e-5, atol=1e-3)     # the last bit of MKL's exp
+    if n == 257:
+        assert np.isnan(ref).any() and np.isposinf(ref).any() and np.isneginf(ref).any()
+        assert (np.isnan(dl).sum(0) > 0).all() and (np.isposinf(dl).sum(0) > 0).all() \
+            and (np.isneginf(dl).sum(0) > 0).all()                            # every column has each
+        zero_inf = np.nonzero((anc[:, 2] == anc[:, 0]) & (dl[:, 2] > 88))[0]
+        assert len(zero_inf) and np.isnan(ref[zero_inf][:, [0, 2]]).all()    # 0 * inf
+        under = np.nonzero(dl[:, 2] == -104)[0]
+        assert (ref[under, 0] == ref[under, 2]).all()                        # exp underflows: zero height
+
+
+@pytest.mark.parametrize("n", bc.ROI_SIZES)
+def test_box_edges_roi_transform(golden, n):
+    g = golden("box_utils_edges.npz")
+    rois, inds = bc.roi_table()
+    assert np.array_equal(rois, g["roi__rois"], equal_nan=True) and np.array_equal(inds, g["roi__inds"], equal_nan=True)
+    with np.errstate(all="ignore"):
+        out = orc.roi_transform(rois[:n], inds[:n], bc.ROI_IMG_H, bc.ROI_IMG_W, bc.ROI_FEAT_H, bc.ROI_FEAT_W)
+    ref = g[f"roi_{n}__boxes"]
+    assert out.dtype == ref.dtype == np.float32 and out.shape == ref.shape == (n, 5)
+    np.testing.assert_array_equal(out, ref)
+    if n == 257:
+        # the table tells divide-then-multiply from multiply-by-reciprocal
+        with np.errstate(all="ignore"):
+            recip = rois[:, 0] * (np.float32(bc.ROI_FEAT_H) / np.float32(bc.ROI_IMG_H))
+        assert (recip[np.isfinite(recip)] != ref[:, 1][np.isfinite(recip)]).any()
+        assert np.isnan(ref).any() and np.isinf(ref).any() and (ref[:, 0] != np.round(ref[:, 0])).any()
+
+
+def test_box_edges_anchors(golden):
+    g = golden("box_utils_edges.npz")
+    for name, (base_size, ratios, scales) in bc.BASE_CASES.items():
+        base = orc.generate_anchor_base(base_size, ratios, scales)
+        assert base.dtype == np.float32 and base.shape == (len(ratios) * len(scales), 4)
+        assert np.array_equal(base, g[f"base_{name}"]), name
+    for name, (bname, stride, w, h) in bc.GRID_CASES.items():
+        a = orc.generate_anchors(g[f"base_{bname}"], stride, w, h)
+        assert a.dtype == np.float32 and a.shape == tuple(g[f"grid_{name}__shape"]), name
+        assert sha(a) == str(g[f"grid_{name}__sha"]), name
+        if f"grid_{name}" in g:
+            assert np.array_equal(a, g[f"grid_{name}"]), name
