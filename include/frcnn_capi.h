@@ -397,6 +397,61 @@ int frcnn_eval_ap(int C, int64_t n_records, const int64_t* hdr, const uint64_t* 
                   const int8_t* rec_flag, int use_07_metric, double* ap, double* map,
                   uint64_t* sorted_key, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ losses */
+
+/* The training losses of one stage, train.py:29-57 with :81-83 (RPN) or
+ * :112-121 (head), forward and backward (DESIGN.md "Losses" is the contract).
+ *   rows = N*L rows (anchors or sampled RoIs of the whole batch), 0 <= rows < 2^31
+ *   cls    fp32 [rows, C]   logits, 2 <= C <= 128
+ *   reg    fp32 [rows, 4P]  P = 1 (RPN: one box per row) or P = C (head: a row
+ *          with label c uses columns 4c..4c+3, the gather of train.py:112-117)
+ *   reg_t  fp64 [rows, 4]   the target creators' regression targets as emitted
+ *   labels int32 [rows] (labels_f64 == 0, frcnn_anchor_target's) or fp64 [rows]
+ *          (labels_f64 != 0, frcnn_proposal_target's gt_roi_label; truncated
+ *          toward zero as .type(LongTensor)).  -1 = unlabelled; a label outside
+ *          -1..C-1 (NaN included) is skipped by both terms, never used as an
+ *          index, and counted
+ *   sigma  > 0, finite; 1/sigma^2, 0.5*sigma^2 and 0.5/sigma^2 are formed in
+ *          double and rounded to fp32, as torch's scalar promotion does
+ * All fp32, every operation separately rounded:
+ *   cls_loss = mean over rows with a label in 0..C-1 of log(sum_c exp(x_c - max x))
+ *              - (x_label - max x); exp and log correctly rounded, the sum in
+ *              ascending class order; no such row -> NaN (0/0, as torch)
+ *   reg_loss = sum over rows with label > 0 and their four columns of
+ *              d < 1/sigma^2 ? (0.5*sigma^2)*(d*d) : d - 0.5/sigma^2, d = |x - (float)t|,
+ *              divided by max(n_pos, 1)
+ * The rows' terms are added in fp64, in an order that depends on rows alone:
+ * the same inputs give the same bits on every call (no atomics).  Only labelled
+ * rows are read: values of cls / reg / reg_t in other rows, NaN included,
+ * influence nothing.
+ * Outputs: loss fp32 [2] = (cls_loss, reg_loss); stats int32 [4] = (n_valid,
+ * n_pos, n_skipped, 0).  rows == 0 gives (NaN, 0) and zero counts; cls, reg,
+ * reg_t and labels may then be NULL.
+ * Workspace: frcnn_losses_workspace_size(rows, C) bytes (0 for arguments
+ * outside the limits).  Two launches. */
+size_t frcnn_losses_workspace_size(int64_t rows, int C);
+int frcnn_losses_fwd(int64_t rows, int C, int P, const float* cls, const float* reg, const double* reg_t,
+                     const void* labels, int labels_f64, double sigma, float* loss, int32_t* stats,
+                     void* workspace, size_t ws_bytes, void* stream);
+
+/* Gradients of the two losses above with respect to cls and reg (the autograd
+ * of train.py:126 through :81-83 / :112-121).  Inputs as frcnn_losses_fwd, plus
+ * its stats and the upstream gradients g_cls / g_reg: DEVICE pointers to one
+ * fp32 each (NULL = 0: that output is all zero and its inputs are not read);
+ * nothing is read back to the host.  Outputs, dense, every element stored
+ * exactly once by one launch (16-byte stores when dcls and dreg are 16-byte
+ * aligned; no memset):
+ *   dcls fp32 [rows, C]  = (softmax(x) - onehot(label)) * (g_cls / n_valid) on
+ *        rows with a label in 0..C-1, 0 elsewhere
+ *   dreg fp32 [rows, 4P] = (d < 1/sigma^2 ? sigma^2*(x - t) : sign(x - t)) *
+ *        (g_reg / max(n_pos, 1)) on the label's four columns of rows with label
+ *        > 0, 0 elsewhere
+ * A NaN logit in an unlabelled row yields a zero gradient here; torch's dense
+ * log-softmax backward would give NaN.  Finite inputs are the contract. */
+int frcnn_losses_bwd(int64_t rows, int C, int P, const float* cls, const float* reg, const double* reg_t,
+                     const void* labels, int labels_f64, double sigma, const int32_t* stats,
+                     const float* g_cls, const float* g_reg, float* dcls, float* dreg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

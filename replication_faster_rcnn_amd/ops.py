@@ -14,6 +14,9 @@
 * ``eval_update(...)`` / ``eval_ap(...)`` -- PASCAL VOC evaluation of those
   detections against ground truth on the device (no reference counterpart:
   its test_eval.py is empty; DESIGN.md "Evaluation").
+* ``rpn_losses(...)`` / ``head_losses(...)`` -- the four training losses of
+  train.py:29-57, :81-83, :112-121, fused, with their own backward (DESIGN.md
+  "Losses").
 
 Two input rules (tests/test_gpu_wrapper_inputs.py):
 
@@ -23,7 +26,7 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   to the current HIP device as contiguous fp32, and results are returned on the
   input's device.  They raise only on shapes that do not belong together.
 * The hot-path ops on device tensors (``propose``, ``roi_transform``,
-  ``detect``, ``eval_update``) convert nothing: every tensor must already be a
+  ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
 
@@ -545,3 +548,124 @@ def roi_transform(rois: torch.Tensor, roi_inds: torch.Tensor, img_h, img_w, feat
                                        float(img_w), int(feat_h), int(feat_w), _lib.ptr(out),
                                        _lib.stream_ptr()), "roi_transform")
     return out
+
+
+# -------------------------------------------------------------------- losses
+_losses_ws = {}  # workspace size per (rows, C) (asked once)
+
+
+class _LossesFunction(torch.autograd.Function):
+    """frcnn_losses_fwd / frcnn_losses_bwd of one stage.  ``cls`` is [N, L, C]
+    contiguous, or (``permuted``) the [N, C, L] view of one; P = 1 (RPN) or C
+    (head).  The backward hands the incoming gradients to the kernel as device
+    pointers (an unused loss: None -> NULL -> that gradient all zero)."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, reg_t, labels, sigma, P, permuted):
+        lib = _lib.load()
+        N, L, C = cls.permute(0, 2, 1).shape if permuted else cls.shape
+        rows = N * L
+        dev = cls.device
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+        need = _losses_ws.get((rows, C))
+        if need is None:
+            need = _losses_ws[(rows, C)] = int(lib.frcnn_losses_workspace_size(rows, C))
+        ws = _lib.cached_workspace("losses", need, dev)
+        f64 = int(labels.dtype == torch.float64)
+        _lib.check(lib.frcnn_losses_fwd(rows, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
+                                        _lib.ptr(labels), f64, sigma, _lib.ptr(loss), _lib.ptr(stats),
+                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "losses forward")
+        ctx.save_for_backward(cls, reg, reg_t, labels, stats)
+        ctx.meta = (N, L, C, P, f64, sigma, permuted)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(stats)
+        return loss[0], loss[1], stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls, g_reg, _g_stats):
+        lib = _lib.load()
+        cls, reg, reg_t, labels, stats = ctx.saved_tensors
+        N, L, C, P, f64, sigma, permuted = ctx.meta
+        for name, g in (("cls_loss", g_cls), ("reg_loss", g_reg)):
+            if g is not None and (g.dtype != torch.float32 or not g.is_cuda or g.numel() != 1):
+                raise RuntimeError(f"losses backward: the gradient of {name} must be one torch.float32 on the "
+                                   f"device; got {g.dtype} on {g.device.type} with {g.numel()} elements")
+        dcls = torch.empty((N, L, C), dtype=torch.float32, device=cls.device)
+        dreg = torch.empty((N, L, 4 * P), dtype=torch.float32, device=cls.device)
+        _lib.check(lib.frcnn_losses_bwd(N * L, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
+                                        _lib.ptr(labels), f64, sigma, _lib.ptr(stats), _lib.ptr(g_cls),
+                                        _lib.ptr(g_reg), _lib.ptr(dcls), _lib.ptr(dreg), _lib.stream_ptr()),
+                   "losses backward")
+        return (dcls.permute(0, 2, 1) if permuted else dcls), dreg, None, None, None, None, None
+
+
+def _losses(op, cls, reg, reg_targets, labels, sigma, head, return_stats):
+    if (not isinstance(labels, torch.Tensor) or labels.dim() != 2
+            or labels.dtype not in (torch.int32, torch.float64)):
+        got = f"{labels.dtype} tensor of shape {list(labels.shape)}" if isinstance(labels, torch.Tensor) \
+            else type(labels).__name__
+        raise RuntimeError(f"{op}: labels must be a contiguous torch.int32 or torch.float64 device tensor of shape "
+                           f"[N, L]; got a {got}")
+    N, L = labels.shape
+    _require(op, "labels", labels, labels.dtype, (N, L))
+    if not isinstance(cls, torch.Tensor) or cls.dim() != 3:
+        raise RuntimeError(f"{op}: cls must be a contiguous torch.float32 device tensor of shape [N, L, C] (or the "
+                           "[N, C, L] permuted view of one)")
+    # [N, L, C] as it lies in memory, or the [N, C, L] view RPN.forward / ResnetHead.forward return
+    permuted = not cls.is_contiguous() and cls.permute(0, 2, 1).is_contiguous()
+    rows_first = cls.permute(0, 2, 1) if permuted else cls
+    C = rows_first.shape[2]
+    _require(op, "cls", rows_first, torch.float32, (N, L, C))
+    P = C if head else 1
+    _require(op, "reg", reg, torch.float32, (N, L, 4 * P))
+    _require(op, "reg_targets", reg_targets, torch.float64, (N, L, 4))
+    if not 2 <= C <= 128:
+        raise RuntimeError(f"{op}: cls has C={C} classes; must be in [2, 128]")
+    sigma = float(sigma)
+    if not 0.0 < sigma < float("inf"):
+        raise RuntimeError(f"{op}: sigma={sigma} must be positive and finite")
+    out = _LossesFunction.apply(cls, reg, reg_targets, labels, sigma, P, permuted)
+    return out if return_stats else out[:2]
+
+
+def rpn_losses(cls: torch.Tensor, reg: torch.Tensor, reg_targets: torch.Tensor, labels: torch.Tensor,
+               sigma: float = 1):
+    """The RPN's two losses (train.py:81-83) in one fused op with its own
+    backward (frcnn_losses_fwd / _bwd; DESIGN.md "Losses" is the contract):
+    cross-entropy over the anchors with label != -1 and smooth-L1 over those
+    with label > 0, divided by max(#positives, 1).
+
+    cls fp32 [N, A, 2] -- or the [N, 2, A] view of one that ``RPN.forward``
+    returns, accepted as it is --, reg fp32 [N, A, 4], reg_targets fp64
+    [N, A, 4] and labels int32 (or fp64) [N, A] exactly as
+    ``targets.anchor_targets`` returns them.  Returns (cls_loss, reg_loss), 0-dim
+    fp32 device tensors.
+
+    A hot-path op: nothing is converted, nothing synchronises.  Every input must
+    be a contiguous device tensor of the dtype and exact shape above
+    (RuntimeError naming the argument otherwise; attribute reads only, before
+    any launch).  Labels outside -1..C-1 are skipped and counted (stats[2] of
+    the C-ABI call), never used as an index.  Values in unlabelled rows, NaN
+    included, influence neither the losses nor the gradients (torch's dense
+    backward would let a NaN logit through; finite inputs are the contract)."""
+    return _losses("rpn_losses", cls, reg, reg_targets, labels, sigma, False, False)
+
+
+def head_losses(cls: torch.Tensor, reg: torch.Tensor, reg_targets: torch.Tensor, labels: torch.Tensor,
+                sigma: float = 1):
+    """The head's two losses (train.py:112-121) as ``rpn_losses``: cls fp32
+    [N, S, C] (or ``ResnetHead.forward``'s [N, C, S] view), reg fp32 [N, S, 4C]
+    ungathered -- a sample with label c uses columns 4c..4c+3, the ``reg_ind``
+    gather of train.py:112-117 done inside the kernel --, reg_targets fp64
+    [N, S, 4] and labels fp64 (or int32) [N, S] exactly as
+    ``targets.proposal_targets`` returns them (fp64 labels truncate toward zero,
+    as ``.type(LongTensor)``).  2 <= C <= 128."""
+    return _losses("head_losses", cls, reg, reg_targets, labels, sigma, True, False)
+
+
+def losses_with_stats(cls, reg, reg_targets, labels, sigma=1, head=False):
+    """``rpn_losses`` / ``head_losses`` (``head``) also returning the int32 [4]
+    device tensor (n_valid, n_pos, n_skipped, 0) of the forward."""
+    return _losses("losses_with_stats", cls, reg, reg_targets, labels, sigma, head, True)
