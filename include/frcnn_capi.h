@@ -452,6 +452,56 @@ int frcnn_losses_bwd(int64_t rows, int C, int P, const float* cls, const float* 
                      const void* labels, int labels_f64, double sigma, const int32_t* stats,
                      const float* g_cls, const float* g_reg, float* dcls, float* dreg, void* stream);
 
+/* ----------------------------------------------------------- preprocessing */
+
+/* The image half of voc_data.__getitem__ (utils/data_loader.py:38,61-75) for a
+ * batch: uint8 HWC RGB images of differing sizes -> fp32 [N,3,out_h,out_w],
+ * resized as skimage.transform.resize does with its defaults and normalised
+ * (DESIGN.md "Preprocessing" is the contract).
+ *   pixels  uint8 [pixels_bytes] (device): image n is h*w*3 bytes, HWC, at
+ *           offset[n]; gaps between images and any order of offsets are allowed
+ *   offset  int64 [N] (device); hw int32 [N,2] = (h, w) per image (device)
+ *   max_h, max_w  host bounds of the batch's sizes: they size the launch and
+ *           its LDS, no size is read back.  1 <= max_h, max_w <= 16384
+ *   1 <= N <= 1024, 1 <= out_h, out_w <= 4096
+ *   mean, std  HOST fp32 [3], finite, std > 0
+ * Anything outside these limits returns FRCNN_EINVAL before any HIP call.
+ * Per channel r = Wh p Ww^T with p = uint8 / 255 and, per axis n_in -> n_out,
+ * W = bilinear x Gaussian:
+ *   bilinear row d: position ((2d+1) n_in - n_out) / (2 n_out) in exact integer
+ *     arithmetic, floor i0 and fraction f; weights 1-f on i0, f on i0+1
+ *   Gaussian (anti-aliasing, only where n_in > n_out): s = (n_in/n_out - 1)/2,
+ *     radius r = int(4s + 0.5), weights exp(-0.5 k^2 / s^2) / sum on i-r..i+r
+ *   indices outside 0..n-1 fold by mirror without edge repeat (period 2(n-1):
+ *     -1 -> 1, n -> n-2; n == 1 -> 0)
+ * and out = (r - mean[c]) / std[c].  The weights are formed in fp64 and rounded
+ * to fp32 once; the sums are fp32 in ascending tap order.  The same image gives
+ * the same bits on every call, alone or in any batch (no atomics).
+ * Outputs, every element stored exactly once (no memset):
+ *   out     fp32 [N,3,out_h,out_w]
+ *   status  int32 [N]: 0 ok; 1 = h or w outside 1..max_h / 1..max_w, or an axis
+ *           with in > 5*out (at 5: s = 2, r = 8, 18 taps); 2 = offset[n] < 0
+ *           or offset[n] + 3*h*w > pixels_bytes.  An image with a nonzero
+ *           status is never read and its three planes are zeros.
+ * Stream-ordered, asynchronous, no allocation, capturable; one launch.
+ * Workspace: frcnn_preprocess_workspace_size(...) bytes (0 for arguments
+ * outside the limits).  This version keeps nothing between launches: the size
+ * is a nominal 256 and the buffer is not touched. */
+size_t frcnn_preprocess_workspace_size(int N, int max_h, int max_w, int out_h, int out_w);
+int frcnn_preprocess(int N, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offset,
+                     const int32_t* hw, int max_h, int max_w, int out_h, int out_w,
+                     const float* mean, const float* std, float* out, int32_t* status,
+                     void* workspace, size_t ws_bytes, void* stream);
+
+/* The boxes' rescale that goes with it (utils/data_loader.py:66-69), fp64:
+ * boxes [N,G,4] as [ymin, xmin, ymax, xmax]; columns 0, 2 are b / h * out_h,
+ * columns 1, 3 are b / w * out_w (divide, then multiply, each rounded); every
+ * negative result becomes -1; an image with h < 1 or w < 1 gets all -1.
+ * Bit-exact with the numpy expression.  1 <= N <= 1024, 0 <= G <= 65536.
+ *   boxes, out double [N,G,4]; hw int32 [N,2]: device.  One launch. */
+int frcnn_rescale_boxes(int N, int G, const double* boxes, const int32_t* hw, int out_h, int out_w,
+                        double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,9 @@ SIGNATURES = {
     "frcnn_losses_workspace_size": (SZ, [I64, I32]),
     "frcnn_losses_fwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, SZ, P]),
     "frcnn_losses_bwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),
+    "frcnn_preprocess_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
+    "frcnn_preprocess": (I32, [I32, P, I64, P, P, I32, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "frcnn_rescale_boxes": (I32, [I32, I32, P, P, I32, I32, P, P]),
 }
 
 # diagnostic entry points of instrumented builds only (not in include/frcnn_capi.h)

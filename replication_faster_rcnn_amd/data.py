@@ -8,10 +8,14 @@ rescaled to ``new_size``, every negative entry set to -1; ``label`` f64 [32]
 with -1 for padding, difficult objects and unparsable objects.  Valid gt rows
 are ``label != -1`` (train.py:74-76).
 
-Host-side by nature (XML text, a few dozen numbers per image): this module is
-the format, not a kernel.  Image decoding / resize / normalisation
-(skimage, torchvision.transforms; utils/data_loader.py:37,70-73) are not on the
-hot path and those libraries are absent here.
+Host-side by nature (XML text, a few dozen numbers per image): the annotation
+half of this module is the format, not a kernel.
+
+The image half (utils/data_loader.py:38,61-75: ``skimage.transform.resize``,
+``ToTensor``, ``Normalize``) runs on the device: ``pack_images`` lays a batch
+of decoded uint8 images into one buffer and ``Preprocessor`` uploads it and
+calls ``ops.preprocess`` / ``ops.rescale_boxes`` (DESIGN.md "Preprocessing").
+Decoding the files (``skimage.io.imread``) stays with the caller.
 """
 from __future__ import annotations
 
@@ -132,3 +136,76 @@ def collate_targets(samples):
     boxes = torch.from_numpy(np.stack([s[0] for s in samples]))
     labels = torch.from_numpy(np.stack([s[1] for s in samples]))
     return boxes, labels
+
+
+def pack_images(images):
+    """A batch of decoded images -> the inputs of ``ops.preprocess``, on the host.
+
+    ``images``: a list of H x W x 3 uint8 numpy arrays or torch tensors (RGB, any
+    strides, sizes may differ).  Anything else -- grayscale, RGBA, another dtype,
+    an empty image -- is rejected with a ValueError naming the image: they are
+    outside the contract, as they are for the reference.  Returns (pixels uint8
+    [B] with the images back to back in list order, pinned when a device is
+    present; offset int64 [N]; hw int32 [N, 2]; (max h, max w)), the first three
+    host tensors ready for a non-blocking upload."""
+    import torch
+    if not isinstance(images, (list, tuple)) or len(images) == 0:
+        raise ValueError("pack_images: images must be a non-empty list of H x W x 3 uint8 arrays")
+    arrs = []
+    for i, im in enumerate(images):
+        if isinstance(im, torch.Tensor):
+            if im.dtype != torch.uint8:
+                raise ValueError(f"pack_images: image {i} has dtype {im.dtype}; must be uint8")
+            im = im.detach().cpu().numpy()
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8:
+            got = f"dtype {im.dtype}" if isinstance(im, np.ndarray) else type(im).__name__
+            raise ValueError(f"pack_images: image {i} must be a uint8 numpy array or tensor; got {got}")
+        if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError(f"pack_images: image {i} has shape {tuple(im.shape)}; must be H x W x 3 (RGB) "
+                             "with H, W >= 1")
+        arrs.append(im)
+    hw = np.array([a.shape[:2] for a in arrs], np.int32)
+    sizes = 3 * hw[:, 0].astype(np.int64) * hw[:, 1]
+    offset = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    pixels = torch.empty(int(sizes.sum()), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    flat = pixels.numpy()
+    for a, o, s in zip(arrs, offset, sizes):
+        flat[o:o + s] = a.reshape(-1)
+    return pixels, torch.from_numpy(offset), torch.from_numpy(hw), (int(hw[:, 0].max()), int(hw[:, 1].max()))
+
+
+class Preprocessor:
+    """``voc_data.__getitem__``'s image branch (utils/data_loader.py:61-75) for a
+    batch, on the device: ``pack_images``, one upload, ``ops.preprocess`` and,
+    with boxes, ``ops.rescale_boxes``.
+
+    ``Preprocessor(new_size)(images, boxes=None)`` -> (image fp32 [N, 3, H, W],
+    boxes fp64 [N, G, 4] or None, hw int32 [N, 2]), all on the device with no
+    synchronisation: what ``Trainer.train_step`` and ``FasterRCNN.predict`` take
+    as they are.  ``boxes``: [N, G, 4] in each image's own pixels, as
+    ``get_labels`` returns them (numpy or tensor).  ``self.status`` keeps the
+    last call's int32 [N] status (device; 0 = ok) for whoever wants to read it."""
+
+    def __init__(self, new_size=(600, 600), mean=None, std=None):
+        self.new_size = (int(new_size[0]), int(new_size[1]))
+        self.mean, self.std = mean, std
+        self.status = None
+
+    def __call__(self, images, boxes=None):
+        import torch
+        from . import _lib, ops
+        pixels, offset, hw, max_hw = pack_images(images)
+        dev = _lib.device()
+        pixels, offset, hw = (t.to(dev, non_blocking=True) for t in (pixels, offset, hw))
+        kw = {}
+        if self.mean is not None:
+            kw["mean"] = self.mean
+        if self.std is not None:
+            kw["std"] = self.std
+        image, self.status = ops.preprocess(pixels, offset, hw, self.new_size, max_hw=max_hw, **kw)
+        if boxes is not None:
+            b = torch.as_tensor(np.asarray(boxes) if not isinstance(boxes, torch.Tensor) else boxes)
+            if b.dim() != 3 or b.shape[0] != len(images) or b.shape[2] != 4:
+                raise ValueError(f"Preprocessor: boxes must be [N={len(images)}, G, 4]; got {tuple(b.shape)}")
+            boxes = ops.rescale_boxes(b.to(dev, torch.float64).contiguous(), hw, self.new_size)
+        return image, boxes, hw

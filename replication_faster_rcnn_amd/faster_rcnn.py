@@ -61,3 +61,22 @@ class FasterRCNN(nn.Module):
         boxes, labels, scores, _, count, _ = det
         return [(boxes[i, :k].to(x.device), labels[i, :k].to(x.device), scores[i, :k].to(x.device))
                 for i, k in enumerate(count.tolist())]
+
+    @torch.no_grad()
+    def predict_images(self, images, new_size=(600, 600), score_thresh=0.05, nms_thresh=0.3, max_det=None):
+        """``predict`` from decoded images: a list of H x W x 3 uint8 arrays of
+        any sizes is resized and normalised on the device
+        (``data.Preprocessor``), run through ``predict`` at ``new_size``, and
+        each image's boxes are mapped back to its own pixels (rows 0, 2 times
+        h / out_h, rows 1, 3 times w / out_w; plain torch on the device).
+        Returns ``predict``'s list; ``self.last_detections`` holds the padded
+        device tensors with the mapped boxes (padding rows stay 0)."""
+        from .data import Preprocessor
+        out_h, out_w = int(new_size[0]), int(new_size[1])
+        x, _, hw = Preprocessor((out_h, out_w))(images)
+        self.predict(x, out_w, out_h, score_thresh=score_thresh, nms_thresh=nms_thresh, max_det=max_det)
+        boxes, labels, scores, roi, count, total = self.last_detections
+        back = (hw.to(torch.float32) / torch.tensor([out_h, out_w], dtype=torch.float32, device=hw.device)).repeat(1, 2)
+        boxes = boxes * back[:, None, :]
+        self.last_detections = (boxes, labels, scores, roi, count, total)
+        return [(boxes[i, :k], labels[i, :k], scores[i, :k]) for i, k in enumerate(count.tolist())]

@@ -17,6 +17,10 @@
 * ``rpn_losses(...)`` / ``head_losses(...)`` -- the four training losses of
   train.py:29-57, :81-83, :112-121, fused, with their own backward (DESIGN.md
   "Losses").
+* ``preprocess(...)`` / ``rescale_boxes(...)`` -- the image half of
+  ``voc_data.__getitem__`` (utils/data_loader.py:38,61-75) for a batch: resize
+  as ``skimage.transform.resize`` does, ``ToTensor``, ``Normalize``, and the
+  boxes' rescale (DESIGN.md "Preprocessing").
 
 Two input rules (tests/test_gpu_wrapper_inputs.py):
 
@@ -26,7 +30,8 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   to the current HIP device as contiguous fp32, and results are returned on the
   input's device.  They raise only on shapes that do not belong together.
 * The hot-path ops on device tensors (``propose``, ``roi_transform``,
-  ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``) convert nothing: every tensor must already be a
+  ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
+  ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
 
@@ -669,3 +674,99 @@ def losses_with_stats(cls, reg, reg_targets, labels, sigma=1, head=False):
     """``rpn_losses`` / ``head_losses`` (``head``) also returning the int32 [4]
     device tensor (n_valid, n_pos, n_skipped, 0) of the forward."""
     return _losses("losses_with_stats", cls, reg, reg_targets, labels, sigma, head, True)
+
+
+# -------------------------------------------------------------- preprocessing
+IMAGE_MEAN = (0.485, 0.456, 0.406)   # utils/data_loader.py:72
+IMAGE_STD = (0.229, 0.224, 0.225)
+PREPROCESS_MAX_RATIO = 5             # an axis may shrink by at most this factor
+_preprocess_cache = {}  # (N, max_h, max_w, out_h, out_w, mean, std) -> (mean[3], std[3], workspace bytes)
+
+
+def _out_size(op, out_size):
+    try:
+        out_h, out_w = (int(v) for v in out_size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{op}: out_size must be (out_h, out_w); got {out_size!r}") from None
+    return out_h, out_w
+
+
+def preprocess(pixels: torch.Tensor, offset: torch.Tensor, hw: torch.Tensor, out_size=(600, 600),
+               mean=IMAGE_MEAN, std=IMAGE_STD, max_hw=None, out=None, status=None):
+    """The image half of ``voc_data.__getitem__`` (utils/data_loader.py:38,61-75)
+    for a batch on the device (frcnn_preprocess; DESIGN.md "Preprocessing" is
+    the contract): ``skimage.transform.resize`` to ``out_size`` with its
+    defaults, ``ToTensor`` and ``Normalize``, one launch.
+
+    pixels uint8 [B]: image n is ``hw[n] = (h, w)`` HWC RGB bytes at
+    ``offset[n]`` (``data.pack_images`` builds all three); offset int64 [N], hw
+    int32 [N, 2].  ``max_hw`` = host-known (max h, max w) of the batch: it sizes
+    the launch, no size is read back.  Without it the largest sizes the kernel
+    accepts (5x ``out_size``) are assumed, which is correct for every batch but
+    runs small tiles -- pass it.  Returns (images fp32 [N, 3, out_h, out_w],
+    status int32 [N]): status 0 ok, 1 a size outside 1..max or an axis shrinking
+    by more than 5, 2 an offset outside ``pixels``; an image with a nonzero
+    status is never read and comes out as zeros.  No synchronisation.
+
+    A hot-path op: every tensor must be a contiguous device tensor of the dtype
+    and exact shape above (RuntimeError naming the argument otherwise)."""
+    lib = _lib.load()
+    op = "preprocess"
+    if not isinstance(pixels, torch.Tensor) or pixels.dim() != 1:
+        raise RuntimeError(f"{op}: pixels must be a contiguous torch.uint8 device tensor of shape [B]")
+    _require(op, "pixels", pixels, torch.uint8, (pixels.shape[0],))
+    if not isinstance(offset, torch.Tensor) or offset.dim() != 1:
+        raise RuntimeError(f"{op}: offset must be a contiguous torch.int64 device tensor of shape [N]")
+    N = offset.shape[0]
+    _require(op, "offset", offset, torch.int64, (N,))
+    _require(op, "hw", hw, torch.int32, (N, 2))
+    out_h, out_w = _out_size(op, out_size)
+    if max_hw is None:
+        max_hw = (min(PREPROCESS_MAX_RATIO * out_h, 16384), min(PREPROCESS_MAX_RATIO * out_w, 16384))
+    max_h, max_w = (int(v) for v in max_hw)
+    key = (N, max_h, max_w, out_h, out_w, tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    cached = _preprocess_cache.get(key)
+    if cached is None:
+        if len(key[5]) != 3 or len(key[6]) != 3:
+            raise RuntimeError(f"{op}: mean and std must have 3 values")
+        need = int(lib.frcnn_preprocess_workspace_size(N, max_h, max_w, out_h, out_w))
+        if need == 0:
+            raise RuntimeError(f"{op}: N={N} must be in [1, 1024], out_size=({out_h}, {out_w}) in [1, 4096] and "
+                               f"max_hw=({max_h}, {max_w}) in [1, 16384]")
+        cached = ((_lib.F32 * 3)(*key[5]), (_lib.F32 * 3)(*key[6]), need)
+        _preprocess_cache[key] = cached
+    mean_c, std_c, need = cached
+    dev = pixels.device
+    if out is None:
+        out = torch.empty((N, 3, out_h, out_w), dtype=torch.float32, device=dev)
+    else:
+        _require(op, "out", out, torch.float32, (N, 3, out_h, out_w))
+    if status is None:
+        status = torch.empty((N,), dtype=torch.int32, device=dev)
+    else:
+        _require(op, "status", status, torch.int32, (N,))
+    ws = _lib.cached_workspace("preprocess", need, dev)
+    _lib.check(lib.frcnn_preprocess(N, _lib.ptr(pixels), pixels.shape[0], _lib.ptr(offset), _lib.ptr(hw), max_h, max_w,
+                                    out_h, out_w, mean_c, std_c, _lib.ptr(out), _lib.ptr(status), _lib.ptr(ws),
+                                    ws.numel(), _lib.stream_ptr()), op)
+    return out, status
+
+
+def rescale_boxes(boxes: torch.Tensor, hw: torch.Tensor, out_size=(600, 600)) -> torch.Tensor:
+    """``data.rescale_boxes`` (utils/data_loader.py:66-69) for a batch on the
+    device, bit-exact with it (frcnn_rescale_boxes): boxes fp64 [N, G, 4] as
+    [ymin, xmin, ymax, xmax] in each image's own pixels, hw int32 [N, 2] ->
+    fp64 [N, G, 4] in ``out_size`` pixels, every negative entry -1; an image
+    with h < 1 or w < 1 gets all -1.  A hot-path op, as ``preprocess``."""
+    lib = _lib.load()
+    op = "rescale_boxes"
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3:
+        raise RuntimeError(f"{op}: boxes must be a contiguous torch.float64 device tensor of shape [N, G, 4]")
+    N, G = boxes.shape[:2]
+    _require(op, "boxes", boxes, torch.float64, (N, G, 4))
+    _require(op, "hw", hw, torch.int32, (N, 2))
+    out_h, out_w = _out_size(op, out_size)
+    out = torch.empty_like(boxes)
+    _lib.check(lib.frcnn_rescale_boxes(N, G, _lib.ptr(boxes), _lib.ptr(hw), out_h, out_w, _lib.ptr(out),
+                                       _lib.stream_ptr()), op)
+    return out

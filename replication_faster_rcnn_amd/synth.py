@@ -111,3 +111,10 @@ def gt_boxes(img_h: int, img_w: int, G: int, seed: int, image_index: int, n_vali
         boxes[g] = b
         labels[g] = float(r.integers(1, 21))
     return np.around(boxes), labels
+
+
+def image(h: int, w: int, seed: int, image_index: int) -> np.ndarray:
+    """A decoded picture's stand-in: uint8 [h, w, 3] RGB, uniform over 0..255
+    (the preprocessing kernel's time does not depend on the pixel values)."""
+    r = rng_for(seed, image_index, 5)
+    return r.integers(0, 256, (h, w, 3), dtype=np.uint8)
