@@ -202,6 +202,39 @@ int frcnn_roi_pool_bwd(const float* grad, const float* rois, const int32_t* argm
  * launch before it is not named). */
 int frcnn_roi_pool_bwd_kernel(int64_t R, int N, int C, int H, int W, int PH, int PW, char* name, size_t len);
 
+/* RoIPool in 16-bit types.  `dtype` is the element type of x / out
+ * (forward) and grad / grad_in (backward); rois, roi_inds and boxes stay fp32 and
+ * argmax int32.  FRCNN_F32 does exactly what the untyped function does.  For
+ * FRCNN_F16 / FRCNN_BF16 every comparison and sum is fp32 on the widened values:
+ * argmax is the fp32 forward's on x widened, out is that forward's output
+ * rounded to nearest even (exact wherever something was selected; a non-empty
+ * bin in which nothing passes the strict '>' gives -inf, the rounded -FLT_MAX),
+ * and grad_in is the fp32 backward's sums in the same order, rounded once at
+ * the write-out.  Same workspaces, launches and frcnn_set_path overrides as the
+ * untyped functions; the one exception is a backward whose planes do not fit
+ * LDS ("roi_pool_bwd_kernel_h<T, false>"), which takes an [N,C,H,W] fp32 scratch
+ * from the stream-ordered allocator for the duration of the kernel.  Any other
+ * dtype code: FRCNN_EINVAL before any HIP call. */
+enum { FRCNN_F32 = 0, FRCNN_F16 = 1, FRCNN_BF16 = 2 };
+int frcnn_roi_pool_fwd_t(int dtype, const void* x, const float* rois, int64_t R, int N, int C, int H, int W,
+                         int PH, int PW, float spatial_scale, int rois_sorted, void* out, int32_t* argmax,
+                         void* workspace, size_t ws_bytes, void* stream);
+int frcnn_roi_pool_fwd_head_t(int dtype, const void* x, const float* rois, const float* roi_inds, int64_t R,
+                              int N, int C, int H, int W, int PH, int PW, float img_h, float img_w,
+                              float spatial_scale, int rois_sorted, float* boxes, void* out, int32_t* argmax,
+                              void* workspace, size_t ws_bytes, void* stream);
+int frcnn_roi_pool_bwd_t(int dtype, const void* grad, const float* rois, const int32_t* argmax, int64_t R,
+                         int N, int C, int H, int W, int PH, int PW, float spatial_scale, void* grad_in,
+                         void* workspace, size_t ws_bytes, void* stream);
+/* The name queries for a dtype: FRCNN_F32 gives the untyped answer, the 16-bit
+ * types name the `_h` sibling with its element type first (e.g.
+ * "roi_pool_fwd_wave_kernel_h<__half, 1024, 16, 7, true, false, 38400>",
+ * "roi_pool_bwd_lead_kernel_h<__hip_bfloat16, 4, 7, 7>"). */
+int frcnn_roi_pool_fwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                int rois_sorted, int head, void* stream, char* name, size_t len);
+int frcnn_roi_pool_bwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW, char* name,
+                                size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

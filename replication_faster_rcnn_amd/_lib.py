@@ -45,6 +45,8 @@ SIGNATURES = {
     "frcnn_set_path": (I32, [ctypes.c_char_p, ctypes.c_char_p]),
     "frcnn_roi_pool_fwd_kernel": (I32, [I64, I32, I32, I32, I32, I32, I32, I32, I32, P, ctypes.c_char_p, SZ]),
     "frcnn_roi_pool_bwd_kernel": (I32, [I64, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_roi_pool_fwd_kernel_t": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, I32, P, ctypes.c_char_p, SZ]),
+    "frcnn_roi_pool_bwd_kernel_t": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_stream_create": (I32, [P, I32, P]),
     "frcnn_stream_destroy": (I32, [P]),
     "frcnn_stream_cu_count": (I32, [P, P]),
@@ -64,6 +66,10 @@ SIGNATURES = {
                                       P, P, P, P, SZ, P]),
     "frcnn_roi_pool_bwd_workspace_size": (SZ, [I64, I32, I32, I32]),
     "frcnn_roi_pool_bwd": (I32, [P, P, P, I64, I32, I32, I32, I32, I32, I32, F32, P, P, SZ, P]),
+    "frcnn_roi_pool_fwd_t": (I32, [I32, P, P, I64, I32, I32, I32, I32, I32, I32, F32, I32, P, P, P, SZ, P]),
+    "frcnn_roi_pool_fwd_head_t": (I32, [I32, P, P, P, I64, I32, I32, I32, I32, I32, I32, F32, F32, F32, I32,
+                                        P, P, P, P, SZ, P]),
+    "frcnn_roi_pool_bwd_t": (I32, [I32, P, P, P, I64, I32, I32, I32, I32, I32, I32, F32, P, P, SZ, P]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),
@@ -101,6 +107,18 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "frcnn_debug_sampler_prof": (I32, [P, I32]),  # -DFRCNN_SAMPLER_PROF (tools/probe_sampler.py)
 }
+
+# frcnn_capi.h's element-type codes of the typed RoIPool entry points
+DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def dtype_code(dtype) -> int:
+    """FRCNN_F32 / FRCNN_F16 / FRCNN_BF16 for a torch dtype (RuntimeError otherwise)."""
+    try:
+        return DTYPE_CODES[dtype]
+    except KeyError:
+        raise RuntimeError(f"RoIPool runs in float32, float16 or bfloat16; got {dtype}") from None
+
 
 _lib = None
 _gpu_checked = False
@@ -231,25 +249,27 @@ def stream_cu_count(stream) -> int:
     return int(n.value)
 
 
-def roi_pool_fwd_kernel(R, N, C, H, W, PH=7, PW=7, rois_sorted=True, head=True, stream=None) -> str:
-    """frcnn_roi_pool_fwd_kernel: the template name of the RoIPool forward kernel
-    a call of this shape launches on `stream` (default: the current stream)."""
+def roi_pool_fwd_kernel(R, N, C, H, W, PH=7, PW=7, rois_sorted=True, head=True, stream=None,
+                        dtype=torch.float32) -> str:
+    """frcnn_roi_pool_fwd_kernel_t: the template name of the RoIPool forward kernel
+    a call of this shape and feature dtype launches on `stream` (default: the
+    current stream)."""
     lib = load()
     s = stream if stream is not None else torch.cuda.current_stream()
-    buf = ctypes.create_string_buffer(128)
-    check(lib.frcnn_roi_pool_fwd_kernel(int(R), int(N), int(C), int(H), int(W), int(PH), int(PW),
-                                        int(bool(rois_sorted)), int(bool(head)),
-                                        ctypes.c_void_p(s.cuda_stream), buf, 128), "roi_pool_fwd_kernel")
+    buf = ctypes.create_string_buffer(160)
+    check(lib.frcnn_roi_pool_fwd_kernel_t(dtype_code(dtype), int(R), int(N), int(C), int(H), int(W), int(PH),
+                                          int(PW), int(bool(rois_sorted)), int(bool(head)),
+                                          ctypes.c_void_p(s.cuda_stream), buf, 160), "roi_pool_fwd_kernel")
     return buf.value.decode()
 
 
-def roi_pool_bwd_kernel(R, N, C, H, W, PH=7, PW=7) -> str:
-    """frcnn_roi_pool_bwd_kernel: the template name of the RoIPool backward kernel
-    a call of this shape launches."""
+def roi_pool_bwd_kernel(R, N, C, H, W, PH=7, PW=7, dtype=torch.float32) -> str:
+    """frcnn_roi_pool_bwd_kernel_t: the template name of the RoIPool backward kernel
+    a call of this shape and gradient dtype launches."""
     lib = load()
-    buf = ctypes.create_string_buffer(128)
-    check(lib.frcnn_roi_pool_bwd_kernel(int(R), int(N), int(C), int(H), int(W), int(PH), int(PW), buf, 128),
-          "roi_pool_bwd_kernel")
+    buf = ctypes.create_string_buffer(160)
+    check(lib.frcnn_roi_pool_bwd_kernel_t(dtype_code(dtype), int(R), int(N), int(C), int(H), int(W), int(PH),
+                                          int(PW), buf, 160), "roi_pool_bwd_kernel")
     return buf.value.decode()
 
 

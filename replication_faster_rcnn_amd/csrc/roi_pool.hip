@@ -18,14 +18,59 @@
 // precomputed per RoI), and such lanes apply their adds in rounds ordered by
 // bin index, so every pixel sees exactly the CPU order n -> ph -> pw.  The
 // finished planes are stored once (zero-fill of grad_in fused).
+//
+// float16 / bfloat16 features and gradients (the `_h` kernels): the same
+// kernels with the element widened at the load and rounded once at the store;
+// tiles, planes, comparisons and sums stay fp32.
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
+#include <type_traits>
+
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+
 #include "common.h"
 
 namespace frcnn {
+
+// Element types of the feature map, the pooled output and the gradients: fp32,
+// or a 16-bit type (DESIGN.md §3 "RoIPool in 16-bit types") that is widened at
+// the load -- every comparison and sum stays fp32 -- and rounded to nearest
+// even once at the store (v_cvt_f32_f16 / v_cvt_f16_f32, a 16-bit shift /
+// v_cvt_pk_bf16_f32; neither direction flushes subnormals).
+__device__ __forceinline__ float ld_f32(const float* p) { return *p; }
+__device__ __forceinline__ float ld_f32(const __half* p) { return __half2float(*p); }
+__device__ __forceinline__ float ld_f32(const __hip_bfloat16* p) { return __bfloat162float(*p); }
+__device__ __forceinline__ __half cvt_elem(float v, const __half*) { return __float2half(v); }
+__device__ __forceinline__ __hip_bfloat16 cvt_elem(float v, const __hip_bfloat16*) { return __float2bfloat16(v); }
+__device__ __forceinline__ void st_f32(float* p, float v) { *p = v; }
+template <class T>
+__device__ __forceinline__ void st_f32(T* p, float v) {
+    *p = cvt_elem(v, p);
+}
+// Four neighbouring elements at an address aligned to four elements: one store
+// (16-bit types: two packed conversions, one 8-byte store).
+__device__ __forceinline__ void st4_f32(float* p, float a, float b, float c, float d) {
+    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+}
+template <class T>
+__device__ __forceinline__ void st4_f32(T* p, float a, float b, float c, float d) {
+    struct alignas(8) Quad {
+        T v[4];
+    };
+    static_assert(sizeof(Quad) == sizeof(uint2), "16-bit element types only");
+    const Quad q{{cvt_elem(a, p), cvt_elem(b, p), cvt_elem(c, p), cvt_elem(d, p)}};
+    *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, q);
+}
+__device__ __forceinline__ void st_nt_f32(float* p, float v) { __builtin_nontemporal_store(v, p); }
+template <class T>
+__device__ __forceinline__ void st_nt_f32(T* p, float v) {
+    static_assert(sizeof(T) == 2, "16-bit element types only");
+    __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, cvt_elem(v, p)), reinterpret_cast<uint16_t*>(p));
+}
 
 constexpr int kMaxBins = 1024;
 constexpr int kListPad = 16;  // entries past each image's RoI list (copies of its last entry)
@@ -56,14 +101,15 @@ __device__ __forceinline__ int4 roi_bin(const float* roi, float ss, int H, int W
     return make_int4(hs, he, ws, we);
 }
 
-__device__ __forceinline__ void pool_window(const float* __restrict__ plane, int W, int4 g,
+template <class T>
+__device__ __forceinline__ void pool_window(const T* __restrict__ plane, int W, int4 g,
                                             float& mv, int& mi) {
     mv = (g.y <= g.x || g.w <= g.z) ? 0.0f : -FLT_MAX;
     mi = -1;
     for (int h = g.x; h < g.y; ++h) {
-        const float* row = plane + h * W;
+        const T* row = plane + h * W;
         for (int w = g.z; w < g.w; ++w) {
-            float v = row[w];
+            float v = ld_f32(&row[w]);
             if (v > mv) {
                 mv = v;
                 mi = h * W + w;
@@ -73,12 +119,17 @@ __device__ __forceinline__ void pool_window(const float* __restrict__ plane, int
 }
 
 // Generic forward: one workgroup per RoI, window gathers served by L1/L2.
-template <bool VEC>
-__global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restrict__ x,
-                                                           const float* __restrict__ rois, int N,
-                                                           int C, int H, int W, int PH, int PW,
-                                                           float ss, float* __restrict__ out,
-                                                           int32_t* __restrict__ argmax) {
+// Every kernel below is a body over the element type T (float, __half,
+// __hip_bfloat16) with two entry points: the fp32 `..._kernel` (its template
+// parameters and so its name are what bench records and profiles key on) and
+// the 16-bit `..._kernel_h<T, ...>`.  The bodies are inlined into the entry
+// points, whose parameters carry the __restrict__.
+template <class T, bool VEC>
+__device__ __forceinline__ void roi_pool_fwd_body(const T* x,
+                                                  const float* rois, int N,
+                                                  int C, int H, int W, int PH, int PW,
+                                                  float ss, T* out,
+                                                  int32_t* argmax) {
     __shared__ int4 bins[kMaxBins];
     const int r = blockIdx.x;
     const int tid = threadIdx.x;
@@ -89,10 +140,10 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restri
     const int b = static_cast<int>(roi[0]);
     const bool valid = b >= 0 && b < N;
     const size_t total = static_cast<size_t>(C) * PHW;
-    float* o = out + static_cast<size_t>(r) * total;
+    T* o = out + static_cast<size_t>(r) * total;
     int32_t* am = argmax + static_cast<size_t>(r) * total;
     const size_t HW = static_cast<size_t>(H) * W;
-    const float* xb = x + (valid ? static_cast<size_t>(b) * C * HW : 0);
+    const T* xb = x + (valid ? static_cast<size_t>(b) * C * HW : 0);
     if (VEC) {
         for (size_t e0 = static_cast<size_t>(tid) * 4; e0 < total; e0 += 1024) {
             int c = static_cast<int>(e0 / PHW);
@@ -112,7 +163,7 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restri
                     ++c;
                 }
             }
-            *reinterpret_cast<float4*>(o + e0) = make_float4(v[0], v[1], v[2], v[3]);
+            st4_f32(o + e0, v[0], v[1], v[2], v[3]);
             *reinterpret_cast<int4*>(am + e0) = make_int4(m[0], m[1], m[2], m[3]);
         }
     } else {
@@ -122,10 +173,28 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restri
             float v = 0.0f;
             int m = -1;
             if (valid) pool_window(xb + c * HW, W, bins[k], v, m);
-            o[e] = v;
+            st_f32(&o[e], v);
             am[e] = m;
         }
     }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float* __restrict__ x,
+                                                           const float* __restrict__ rois, int N,
+                                                           int C, int H, int W, int PH, int PW,
+                                                           float ss, float* __restrict__ out,
+                                                           int32_t* __restrict__ argmax) {
+    roi_pool_fwd_body<float, VEC>(x, rois, N, C, H, W, PH, PW, ss, out, argmax);
+}
+
+template <class T, bool VEC>
+__global__ __launch_bounds__(256) void roi_pool_fwd_kernel_h(const T* __restrict__ x,
+                                                             const float* __restrict__ rois, int N,
+                                                             int C, int H, int W, int PH, int PW,
+                                                             float ss, T* __restrict__ out,
+                                                             int32_t* __restrict__ argmax) {
+    roi_pool_fwd_body<T, VEC>(x, rois, N, C, H, W, PH, PW, ss, out, argmax);
 }
 
 // RoI geometry shared by all bins: start (sh, sw) and bin size (bh, bw).
@@ -245,11 +314,11 @@ constexpr int kDenseMisc = 64;
 __host__ __device__ constexpr size_t dense_fixed_bytes() { return 256 * 4 + kDenseMisc * 4; }
 __host__ __device__ constexpr size_t dense_item_bytes() { return 16 + 4 + 4 + 1; }
 
-template <int NT, int CG, int FIX, bool HEAD, bool LIST>
-__global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel(
-    const float* __restrict__ x, const float* __restrict__ rois, const int* __restrict__ list,
-    const int* __restrict__ cnt, int R, int C, int H, int W, int PH_, int PW_, float ss,
-    float* __restrict__ out, int32_t* __restrict__ argmax, int cap, HeadArgs hd) {
+template <class T, int NT, int CG, int FIX, bool HEAD, bool LIST>
+__device__ __forceinline__ void roi_pool_fwd_dense_body(
+    const T* x, const float* rois, const int* list,
+    const int* cnt, int R, int C, int H, int W, int PH_, int PW_, float ss,
+    T* out, int32_t* argmax, int cap, HeadArgs hd) {
     constexpr int NP = CG / 4;
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) float4 q4[];
@@ -303,7 +372,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel(
                 const int rem = e - t * (CG * PHW);
                 const int r = t < n_lo ? t : rg.y + (t - n_lo);
                 const size_t o = (static_cast<size_t>(r) * C + c0) * PHW + rem;
-                out[o] = 0.0f;
+                st_f32(&out[o], 0.0f);
                 argmax[o] = -1;
             }
             return;
@@ -364,12 +433,12 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel(
 
     // ---- 2. stage the CG planes (NaN -> -inf: never selected by the strict '>'
     // against the -FLT_MAX start, and max3 never sees a NaN)
-    const float* src = x + (static_cast<size_t>(b) * C + c0) * HW;
+    const T* src = x + (static_cast<size_t>(b) * C + c0) * HW;
     for (int p = tid; p < HW; p += NT) {
         float v[CG];
 #pragma unroll
         for (int q = 0; q < CG; ++q) {
-            const float e = src[static_cast<size_t>(q) * HW + p];
+            const float e = ld_f32(&src[static_cast<size_t>(q) * HW + p]);
             v[q] = e != e ? -INFINITY : e;
         }
 #pragma unroll
@@ -513,13 +582,31 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel(
                     float v = mv[c];
                     if (v == 0.0f && idx >= 0)  // exact bits (sign) of a zero maximum
                         v = reinterpret_cast<const float*>(tb + (c >> 2) * plane_bytes)[idx * 4 + (c & 3)];
-                    out[o + static_cast<size_t>(c) * PHW] = v;
+                    st_f32(&out[o + static_cast<size_t>(c) * PHW], v);
                     argmax[o + static_cast<size_t>(c) * PHW] = idx;
                 }
             }
             f0 = __builtin_amdgcn_readfirstlane(fn);
         }
     }
+}
+
+template <int NT, int CG, int FIX, bool HEAD, bool LIST>
+__global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel(
+    const float* __restrict__ x, const float* __restrict__ rois, const int* __restrict__ list,
+    const int* __restrict__ cnt, int R, int C, int H, int W, int PH_, int PW_, float ss,
+    float* __restrict__ out, int32_t* __restrict__ argmax, int cap, HeadArgs hd) {
+    roi_pool_fwd_dense_body<float, NT, CG, FIX, HEAD, LIST>(x, rois, list, cnt, R, C, H, W, PH_, PW_, ss, out,
+                                                            argmax, cap, hd);
+}
+
+template <class T, int NT, int CG, int FIX, bool HEAD, bool LIST>
+__global__ __launch_bounds__(NT) void roi_pool_fwd_dense_kernel_h(
+    const T* __restrict__ x, const float* __restrict__ rois, const int* __restrict__ list,
+    const int* __restrict__ cnt, int R, int C, int H, int W, int PH_, int PW_, float ss,
+    T* __restrict__ out, int32_t* __restrict__ argmax, int cap, HeadArgs hd) {
+    roi_pool_fwd_dense_body<T, NT, CG, FIX, HEAD, LIST>(x, rois, list, cnt, R, C, H, W, PH_, PW_, ss, out, argmax,
+                                                        cap, hd);
 }
 
 // Timeline probe of the wave-per-RoI forward (instrumented builds only,
@@ -607,10 +694,10 @@ __device__ __forceinline__ void tile_read(uint32_t a, uint32_t ps, f32x4 (&v)[NP
 // DESIGN.md §3, profiles/r5_experiments.md.)
 // FIX = PH = PW known at compile time (the 7x7 head): the 2 x CG output
 // stores of a RoI take immediate offsets from one base address.
-template <int NT, int CG, int FIX, bool HEAD, bool NTS = false, int KPS = 0>
-__global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
-    const float* __restrict__ x, const float* __restrict__ rois, int R, int C, int H, int W, int PH_, int PW_,
-    float ss, float* __restrict__ out, int32_t* __restrict__ argmax, int geo_cap, HeadArgs hd) {
+template <class T, int NT, int CG, int FIX, bool HEAD, bool NTS, int KPS>
+__device__ __forceinline__ void roi_pool_fwd_wave_body(
+    const T* x, const float* rois, int R, int C, int H, int W, int PH_, int PW_,
+    float ss, T* out, int32_t* argmax, int geo_cap, HeadArgs hd) {
     const int PH = FIX ? FIX : PH_, PW = FIX ? FIX : PW_;
     constexpr int NP = CG / 4;
     // tile (NP planes of PS bytes, from address 0), geometry chunk, reduction
@@ -650,7 +737,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
             const int rem = e - t * (CG * PHW);
             const int r = t < n_lo ? t : rg.y + (t - n_lo);
             const size_t o = (static_cast<size_t>(r) * C + c0) * PHW + rem;
-            out[o] = 0.0f;
+            st_f32(&out[o], 0.0f);
             argmax[o] = -1;
         }
         return;
@@ -662,7 +749,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
     if (z >= nr) return;
     const int nmine = (nr - z + split - 1) / split;  // items z, z+split, ...
     PPROF_ROIS(nmine);
-    const float* src = x + (static_cast<size_t>(b) * C + c0) * HW;
+    const T* src = x + (static_cast<size_t>(b) * C + c0) * HW;
     if (tid < NP) *reinterpret_cast<float4*>(t + tid * PS + HW * 16) = make_float4(0.f, 0.f, 0.f, 0.f);
     // Staged as max(v, -FLT_MAX) with NaN -> -FLT_MAX: no such value passes the
     // scan's strict '>' against a running maximum >= -FLT_MAX, and the window's
@@ -671,7 +758,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
         float v[CG];
 #pragma unroll
         for (int q = 0; q < CG; ++q) {
-            const float e = src[static_cast<size_t>(q) * HW + p];
+            const float e = ld_f32(&src[static_cast<size_t>(q) * HW + p]);
             v[q] = e > -FLT_MAX ? e : -FLT_MAX;
         }
 #pragma unroll
@@ -763,7 +850,7 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
             }
             if (act) {
                 const size_t o = (static_cast<size_t>(r) * C + c0) * PHW + lane;
-                float* op = out + o;
+                T* op = out + o;
                 int32_t* ap = argmax + o;
                 if constexpr (NTS) {  // (a template choice: a runtime branch gets its stores
                                       // merged with the temporal ones, hint dropped)
@@ -774,13 +861,13 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
                     // and a real head reads the outputs next, so temporal is the default
 #pragma unroll
                     for (int c = 0; c < CG; ++c) {
-                        __builtin_nontemporal_store(mv[c], op + c * PHW);
+                        st_nt_f32(&op[c * PHW], mv[c]);
                         __builtin_nontemporal_store(mi[c] >> 4, ap + c * PHW);
                     }
                 } else {
 #pragma unroll
                     for (int c = 0; c < CG; ++c) {
-                        op[c * PHW] = mv[c];
+                        st_f32(&op[c * PHW], mv[c]);
                         ap[c * PHW] = mi[c] >> 4;
                     }
                 }
@@ -790,6 +877,22 @@ __global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
         __syncthreads();  // the chunk's geometry and s_next are reused
     }
     PPROF_T(3);
+}
+
+template <int NT, int CG, int FIX, bool HEAD, bool NTS = false, int KPS = 0>
+__global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel(
+    const float* __restrict__ x, const float* __restrict__ rois, int R, int C, int H, int W, int PH_, int PW_,
+    float ss, float* __restrict__ out, int32_t* __restrict__ argmax, int geo_cap, HeadArgs hd) {
+    roi_pool_fwd_wave_body<float, NT, CG, FIX, HEAD, NTS, KPS>(x, rois, R, C, H, W, PH_, PW_, ss, out, argmax,
+                                                               geo_cap, hd);
+}
+
+template <class T, int NT, int CG, int FIX, bool HEAD, bool NTS = false, int KPS = 0>
+__global__ __launch_bounds__(NT) void roi_pool_fwd_wave_kernel_h(
+    const T* __restrict__ x, const float* __restrict__ rois, int R, int C, int H, int W, int PH_, int PW_,
+    float ss, T* __restrict__ out, int32_t* __restrict__ argmax, int geo_cap, HeadArgs hd) {
+    roi_pool_fwd_wave_body<T, NT, CG, FIX, HEAD, NTS, KPS>(x, rois, R, C, H, W, PH_, PW_, ss, out, argmax, geo_cap,
+                                                           hd);
 }
 
 // nets/heads.py:42-47 (fp32 divide, then multiply) + [idx, box] pack.
@@ -863,13 +966,14 @@ __global__ __launch_bounds__(1024) void roi_lists_kernel(const float* __restrict
 
 // Outputs of RoIs with an out-of-range batch index: 0 / -1 (torchvision: UB);
 // with a head transform (hd.inds) also their [idx, box] rows.
-__global__ __launch_bounds__(256) void roi_pool_invalid_fill_kernel(const int* __restrict__ list,
-                                                                    const int* __restrict__ cnt,
-                                                                    int R, int N, size_t per_roi,
-                                                                    float* __restrict__ out,
-                                                                    int32_t* __restrict__ argmax,
-                                                                    const float* __restrict__ rois4 = nullptr,
-                                                                    HeadArgs hd = HeadArgs{}) {
+template <class T>
+__device__ __forceinline__ void roi_pool_invalid_fill_body(const int* list,
+                                                           const int* cnt,
+                                                           int R, int N, size_t per_roi,
+                                                           T* out,
+                                                           int32_t* argmax,
+                                                           const float* rois4,
+                                                           HeadArgs hd) {
     const int n = cnt[N];
     for (int t = blockIdx.x; t < n; t += gridDim.x) {
         const int r = list[static_cast<size_t>(N) * list_stride(R) + t];
@@ -881,10 +985,31 @@ __global__ __launch_bounds__(256) void roi_pool_invalid_fill_kernel(const int* _
             for (int j = 0; j < 5; ++j) hd.boxes[static_cast<size_t>(r) * 5 + j] = bx[j];
         }
         for (size_t e = threadIdx.x; e < per_roi; e += 256) {
-            out[base + e] = 0.0f;
+            st_f32(&out[base + e], 0.0f);
             argmax[base + e] = -1;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void roi_pool_invalid_fill_kernel(const int* __restrict__ list,
+                                                                    const int* __restrict__ cnt,
+                                                                    int R, int N, size_t per_roi,
+                                                                    float* __restrict__ out,
+                                                                    int32_t* __restrict__ argmax,
+                                                                    const float* __restrict__ rois4 = nullptr,
+                                                                    HeadArgs hd = HeadArgs{}) {
+    roi_pool_invalid_fill_body(list, cnt, R, N, per_roi, out, argmax, rois4, hd);
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void roi_pool_invalid_fill_kernel_h(const int* __restrict__ list,
+                                                                      const int* __restrict__ cnt,
+                                                                      int R, int N, size_t per_roi,
+                                                                      T* __restrict__ out,
+                                                                      int32_t* __restrict__ argmax,
+                                                                      const float* __restrict__ rois4,
+                                                                      HeadArgs hd) {
+    roi_pool_invalid_fill_body(list, cnt, R, N, per_roi, out, argmax, rois4, hd);
 }
 
 // ------------------------------------------------------------------ backward
@@ -1055,20 +1180,70 @@ __global__ __launch_bounds__(1024) void roi_bwd_prep_lists_kernel(const float* _
 
 // General plane-owner backward (any output size; planes in LDS or, when a
 // plane does not fit, in grad_in itself with agent-scope load/store rounds).
-template <bool IN_LDS>
-__global__ void roi_pool_bwd_kernel(const float* __restrict__ grad,
-                                    const int32_t* __restrict__ argmax,
-                                    const uint64_t* __restrict__ cmask,
-                                    const int* __restrict__ list, const int* __restrict__ cnt,
-                                    int R, int C, int HW, int PHW, int CPW,
-                                    float* __restrict__ grad_in) {
+// The prefetch rings of the backward kernels keep a gradient as the raw word
+// its load returns (fp32: the value; 16-bit: the zero-extended element) and
+// widen it when the slot is taken, so no conversion waits on a load in flight.
+template <class T>
+using RawElem = std::conditional_t<std::is_same_v<T, float>, float, uint32_t>;
+__device__ __forceinline__ float ld_raw(const float* p) { return *p; }
+template <class T>
+__device__ __forceinline__ uint32_t ld_raw(const T* p) {
+    static_assert(sizeof(T) == 2, "16-bit element types only");
+    return *reinterpret_cast<const uint16_t*>(p);
+}
+__device__ __forceinline__ float raw_f32(float r, const float*) { return r; }
+__device__ __forceinline__ float raw_f32(uint32_t r, const __half*) {
+    return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(r)));
+}
+__device__ __forceinline__ float raw_f32(uint32_t r, const __hip_bfloat16*) { return __uint_as_float(r << 16); }
+
+// A finished fp32 plane (LDS, or the global scratch plane of the 16-bit
+// global-memory path) to its place in grad_in: the one rounding of a 16-bit
+// backward.  Four pixels per store where the plane size allows.
+template <class T>
+__device__ __forceinline__ void plane_write_out(const float* plane, T* gplane, int HW, int lane) {
+    if constexpr (std::is_same_v<T, float>) {
+        if ((HW & 3) == 0) {
+            const float4* s4 = reinterpret_cast<const float4*>(plane);
+            float4* d4 = reinterpret_cast<float4*>(gplane);
+            for (int i = lane; i < HW / 4; i += 64) d4[i] = s4[i];
+        } else {
+            for (int i = lane; i < HW; i += 64) gplane[i] = plane[i];
+        }
+    } else {
+        if ((HW & 3) == 0) {  // plane starts are then 8-byte aligned
+            const float4* s4 = reinterpret_cast<const float4*>(plane);
+            for (int i = lane; i < HW / 4; i += 64) {
+                const float4 v = s4[i];
+                st4_f32(gplane + 4 * i, v.x, v.y, v.z, v.w);
+            }
+        } else {
+            for (int i = lane; i < HW; i += 64) st_f32(gplane + i, plane[i]);
+        }
+    }
+}
+
+// `fplanes`: with a 16-bit T and IN_LDS false, the [N,C,HW] fp32 scratch the
+// planes are summed in before they are rounded into grad_in (fp32: grad_in
+// itself holds them, fplanes is unused).
+template <class T, bool IN_LDS>
+__device__ __forceinline__ void roi_pool_bwd_body(const T* grad,
+                                                  const int32_t* argmax,
+                                                  const uint64_t* cmask,
+                                                  const int* list, const int* cnt,
+                                                  int R, int C, int HW, int PHW, int CPW,
+                                                  T* grad_in, float* fplanes) {
     extern __shared__ __attribute__((aligned(16))) float planes[];
+    constexpr bool kF32 = std::is_same_v<T, float>;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int c = blockIdx.x * CPW + wid;
     if (c >= C) return;  // whole wave; no workgroup barrier below
-    float* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
-    float* plane = IN_LDS ? planes + static_cast<size_t>(wid) * HW : gplane;
+    T* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
+    float* plane;
+    if constexpr (IN_LDS) plane = planes + static_cast<size_t>(wid) * HW;
+    else if constexpr (kF32) plane = gplane;
+    else plane = fplanes + (static_cast<size_t>(b) * C + c) * HW;
     for (int i = lane; i < HW; i += 64) {
         if (IN_LDS) plane[i] = 0.0f;
         else __hip_atomic_store(plane + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1083,7 +1258,7 @@ __global__ void roi_pool_bwd_kernel(const float* __restrict__ grad,
             const int k = k0 + lane;
             const bool act = k < PHW;
             const int am = act ? argmax[base + k] : -1;
-            const float g = act ? grad[base + k] : 0.0f;
+            const float g = act ? ld_f32(&grad[base + k]) : 0.0f;
             uint64_t pend = (act && am != -1) ? cmask[static_cast<size_t>(n) * PHW + k] : 0ull;
             int depth = 0;
             while (__ballot(pend != 0)) {
@@ -1112,15 +1287,34 @@ __global__ void roi_pool_bwd_kernel(const float* __restrict__ grad,
             }
         }
     }
-    if (IN_LDS) {
-        if ((HW & 3) == 0) {
-            const float4* s4 = reinterpret_cast<const float4*>(plane);
-            float4* d4 = reinterpret_cast<float4*>(gplane);
-            for (int i = lane; i < HW / 4; i += 64) d4[i] = s4[i];
-        } else {
-            for (int i = lane; i < HW; i += 64) gplane[i] = plane[i];
-        }
+    if constexpr (IN_LDS) {
+        plane_write_out(plane, gplane, HW, lane);
+    } else if constexpr (!kF32) {
+        // the last round's stores have landed (s_waitcnt above); the scratch plane is
+        // read back at the scope it was written with and rounded once
+        for (int i = lane; i < HW; i += 64)
+            st_f32(gplane + i, __hip_atomic_load(plane + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
+}
+
+template <bool IN_LDS>
+__global__ void roi_pool_bwd_kernel(const float* __restrict__ grad,
+                                    const int32_t* __restrict__ argmax,
+                                    const uint64_t* __restrict__ cmask,
+                                    const int* __restrict__ list, const int* __restrict__ cnt,
+                                    int R, int C, int HW, int PHW, int CPW,
+                                    float* __restrict__ grad_in) {
+    roi_pool_bwd_body<float, IN_LDS>(grad, argmax, cmask, list, cnt, R, C, HW, PHW, CPW, grad_in, nullptr);
+}
+
+template <class T, bool IN_LDS>
+__global__ void roi_pool_bwd_kernel_h(const T* __restrict__ grad,
+                                      const int32_t* __restrict__ argmax,
+                                      const uint64_t* __restrict__ cmask,
+                                      const int* __restrict__ list, const int* __restrict__ cnt,
+                                      int R, int C, int HW, int PHW, int CPW,
+                                      T* __restrict__ grad_in, float* __restrict__ fplanes) {
+    roi_pool_bwd_body<T, IN_LDS>(grad, argmax, cmask, list, cnt, R, C, HW, PHW, CPW, grad_in, fplanes);
 }
 
 // Same plane-owner backward for PH*PW <= 64 (one bin per lane, the 7x7 head),
@@ -1129,12 +1323,12 @@ __global__ void roi_pool_bwd_kernel(const float* __restrict__ grad,
 // indices come by scalar loads, so no vector load sits between the ring's loads
 // in the in-order vmcnt queue.  Summation order per pixel is unchanged (RoIs
 // ascending, bins ascending within a RoI): bit-identical results.
-template <int D>
-__global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
-    const float* __restrict__ grad, const int32_t* __restrict__ argmax,
-    const uint64_t* __restrict__ cmask, const uint8_t* __restrict__ code,
-    const int* __restrict__ list, const int* __restrict__ cnt,
-    int R, int C, int HW, int PHW, int PW, int CPW, float* __restrict__ grad_in) {
+template <class T, int D>
+__device__ __forceinline__ void roi_pool_bwd_pf_body(
+    const T* grad, const int32_t* argmax,
+    const uint64_t* cmask, const uint8_t* code,
+    const int* list, const int* cnt,
+    int R, int C, int HW, int PHW, int PW, int CPW, T* grad_in) {
     extern __shared__ __attribute__((aligned(16))) float planes[];
     const int lane = threadIdx.x & 63;
     // wave-uniform in an SGPR: the per-RoI grad / argmax bases are then scalar,
@@ -1143,7 +1337,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
     const int b = blockIdx.y;
     const int c = blockIdx.x * CPW + wid;
     if (c >= C) return;  // whole wave; no workgroup barrier below
-    float* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
+    T* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
     float* plane = planes + static_cast<size_t>(wid) * HW;
     for (int i = lane; i < HW; i += 64) plane[i] = 0.0f;
     const int nr = cnt[b];
@@ -1166,7 +1360,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
         // for the whole vmcnt queue at the branch join, which undoes the ring.
         const int kl = act ? lane : 0;
         int am_r[D];
-        float g_r[D];
+        RawElem<T> g_r[D];
         uint32_t cd_r[D];
         uint64_t cm_r[D];  // full overlap mask, used only by RoIs flagged slow
 #pragma unroll
@@ -1175,7 +1369,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
             const size_t base = (static_cast<size_t>(n) * C + c) * PHW;
             const size_t nb = static_cast<size_t>(n) * PHW;
             am_r[d] = (argmax + base)[kl];
-            g_r[d] = (grad + base)[kl];
+            g_r[d] = ld_raw(grad + base + kl);
             cd_r[d] = (code + nb)[kl];
             cm_r[d] = (cmask + nb)[kl];
             // keep the loop's issue order (slot by slot): the waitcnt pass then
@@ -1201,10 +1395,11 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
                 // compiler cannot coalesce away) so the refill lands in the
                 // slot's own registers: no back-edge copy, no wait on it.
                 int am;
-                float g;
+                RawElem<T> gw;
                 uint32_t cd;
                 asm volatile("v_mov_b32 %0, %1" : "=v"(am) : "v"(am_r[d]));
-                asm volatile("v_mov_b32 %0, %1" : "=v"(g) : "v"(g_r[d]));
+                asm volatile("v_mov_b32 %0, %1" : "=v"(gw) : "v"(g_r[d]));
+                const float g = raw_f32(gw, grad);
                 asm volatile("v_mov_b32 %0, %1" : "=v"(cd) : "v"(cd_r[d]));
                 uint32_t cm_lo, cm_hi;
                 asm volatile("v_mov_b32 %0, %1" : "=v"(cm_lo) : "v"(static_cast<uint32_t>(cm_r[d])));
@@ -1215,7 +1410,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
                     const size_t base = (static_cast<size_t>(n) * C + c) * PHW;
                     const size_t nb = static_cast<size_t>(n) * PHW;
                     am_r[d] = (argmax + base)[kl];
-                    g_r[d] = (grad + base)[kl];
+                    g_r[d] = ld_raw(grad + base + kl);
                     cd_r[d] = (code + nb)[kl];
                     cm_r[d] = (cmask + nb)[kl];
                 }
@@ -1253,15 +1448,26 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if ((HW & 3) == 0) {
-        const float4* s4 = reinterpret_cast<const float4*>(plane);
-        float4* d4 = reinterpret_cast<float4*>(gplane);
-        for (int i = lane; i < HW / 4; i += 64) d4[i] = s4[i];
-    } else {
-        for (int i = lane; i < HW; i += 64) gplane[i] = plane[i];
-    }
+    plane_write_out(plane, gplane, HW, lane);
 }
 
+template <int D>
+__global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel(
+    const float* __restrict__ grad, const int32_t* __restrict__ argmax,
+    const uint64_t* __restrict__ cmask, const uint8_t* __restrict__ code,
+    const int* __restrict__ list, const int* __restrict__ cnt,
+    int R, int C, int HW, int PHW, int PW, int CPW, float* __restrict__ grad_in) {
+    roi_pool_bwd_pf_body<float, D>(grad, argmax, cmask, code, list, cnt, R, C, HW, PHW, PW, CPW, grad_in);
+}
+
+template <class T, int D>
+__global__ __launch_bounds__(1024) void roi_pool_bwd_pf_kernel_h(
+    const T* __restrict__ grad, const int32_t* __restrict__ argmax,
+    const uint64_t* __restrict__ cmask, const uint8_t* __restrict__ code,
+    const int* __restrict__ list, const int* __restrict__ cnt,
+    int R, int C, int HW, int PHW, int PW, int CPW, T* __restrict__ grad_in) {
+    roi_pool_bwd_pf_body<T, D>(grad, argmax, cmask, code, list, cnt, R, C, HW, PHW, PW, CPW, grad_in);
+}
 
 // Phase timer of the leader backward (-DFRCNN_BWD_PROF, tools/probe_bwd_spans.py):
 // per wave, the RoI count, start and end on the constant 100 MHz clock
@@ -1308,11 +1514,11 @@ constexpr int kBwdXRow = 80;
 // pair's exchange (after it, when the pair holds a flagged RoI: its gather reads
 // the row).  PHT = PH at compile time (the 7x7 head: the gather's reads all
 // issued at once), or 0.
-template <int D, int PWT, int PHT>
-__global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
-    const float* __restrict__ grad, const int32_t* __restrict__ argmax,
-    const int* __restrict__ list, const int* __restrict__ cnt,
-    int R, int C, int HW, int HWs, int PH_, int CPW, float* __restrict__ grad_in) {
+template <class T, int D, int PWT, int PHT>
+__device__ __forceinline__ void roi_pool_bwd_lead_body(
+    const T* grad, const int32_t* argmax,
+    const int* list, const int* cnt,
+    int R, int C, int HW, int HWs, int PH_, int CPW, T* grad_in) {
     extern __shared__ __attribute__((aligned(16))) float planes[];
     static_assert(PWT == 7, "exchange rows hold 7 bins and a pad");
     constexpr int PW = PWT;
@@ -1330,7 +1536,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long tq[2] = {0, 0};
 #endif
-    float* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
+    T* gplane = grad_in + (static_cast<size_t>(b) * C + c) * HW;
     // HWs >= HW + 64: word HW + lane is lane's dummy (a word per lane, so the
     // non-leaders' writes do not serialise on one bank)
     float* plane = planes + static_cast<size_t>(wid) * HWs;
@@ -1357,12 +1563,20 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
         const uint32_t kl = act ? lane : 0;
         // the host guarantees R*C*PHW*4 < 2^31: byte offsets fit the descriptors
         const uint32_t gb = static_cast<uint32_t>(R) * C * PHW * 4;
-        const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(grad), 0, gb, 0x00020000);
+        const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(grad), 0, gb / 4 * sizeof(T), 0x00020000);
         const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(argmax), 0, gb, 0x00020000);
         const uint32_t cpb = static_cast<uint32_t>(c) * PHW * 4;
         const uint32_t rpb = static_cast<uint32_t>(C) * PHW * 4;
         int am_r[D], fl_r[D];
-        float g_r[D];
+        RawElem<T> g_r[D];
+        // `so`: the RoI's byte offset in argmax (4-byte elements, the list flag dropped
+        // out); a 16-bit gradient sits at half of it
+        auto load_g = [&](uint32_t so) -> RawElem<T> {
+            if constexpr (std::is_same_v<T, float>)
+                return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, kl * 4, so, 0));
+            else
+                return __builtin_amdgcn_raw_buffer_load_b16(rs_g, kl * 2, so >> 1, 0);
+        };
         // list entries: RoI index | flag << 31 (roi_bwd_prep_lists_kernel);
         // the flag drops out of the byte offsets (index x an even stride, mod
         // 2^32).  Positions past the image's RoIs hold copies of its last entry
@@ -1375,7 +1589,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
             fl_r[d] = e < 0;
             const uint32_t so = static_cast<uint32_t>(e) * rpb + cpb;
             am_r[d] = __builtin_amdgcn_raw_buffer_load_b32(rs_a, kl * 4, so, 0);
-            g_r[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, kl * 4, so, 0));
+            g_r[d] = load_g(so);
             asm volatile("" ::: "memory");
         }
         for (int t0 = 0; t0 < nr; t0 += D) {
@@ -1389,14 +1603,16 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 asm volatile("v_mov_b32 %0, %1" : "=v"(am[d]) : "v"(am_r[d]));
-                asm volatile("v_mov_b32 %0, %1" : "=v"(g[d]) : "v"(g_r[d]));
+                RawElem<T> graw;
+                asm volatile("v_mov_b32 %0, %1" : "=v"(graw) : "v"(g_r[d]));
+                g[d] = raw_f32(graw, grad);
                 const bool live = t0 + d < nr;
                 slow[d] = live && fl_r[d];
                 am[d] = live ? am[d] : -1;
                 am[d] = act ? am[d] : -2;
                 const uint32_t so = static_cast<uint32_t>(nx[d]) * rpb + cpb;
                 am_r[d] = __builtin_amdgcn_raw_buffer_load_b32(rs_a, kl * 4, so, 0);
-                g_r[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_g, kl * 4, so, 0));
+                g_r[d] = load_g(so);
                 fl_r[d] = nx[d] < 0;
             }
             // The exchange of slot pair k + 1 is issued before the read-add-writes of pair k
@@ -1535,13 +1751,7 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if ((HW & 3) == 0) {
-        const float4* s4 = reinterpret_cast<const float4*>(plane);
-        float4* d4 = reinterpret_cast<float4*>(gplane);
-        for (int i = lane; i < HW / 4; i += 64) d4[i] = s4[i];
-    } else {
-        for (int i = lane; i < HW; i += 64) gplane[i] = plane[i];
-    }
+    plane_write_out(plane, gplane, HW, lane);
 #ifdef FRCNN_BWD_PROF
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
@@ -1554,6 +1764,22 @@ __global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
         g_bwd_prof[gw][7] = tq[1];
     }
 #endif
+}
+
+template <int D, int PWT, int PHT>
+__global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel(
+    const float* __restrict__ grad, const int32_t* __restrict__ argmax,
+    const int* __restrict__ list, const int* __restrict__ cnt,
+    int R, int C, int HW, int HWs, int PH_, int CPW, float* __restrict__ grad_in) {
+    roi_pool_bwd_lead_body<float, D, PWT, PHT>(grad, argmax, list, cnt, R, C, HW, HWs, PH_, CPW, grad_in);
+}
+
+template <class T, int D, int PWT, int PHT>
+__global__ __launch_bounds__(1024) void roi_pool_bwd_lead_kernel_h(
+    const T* __restrict__ grad, const int32_t* __restrict__ argmax,
+    const int* __restrict__ list, const int* __restrict__ cnt,
+    int R, int C, int HW, int HWs, int PH_, int CPW, T* __restrict__ grad_in) {
+    roi_pool_bwd_lead_body<T, D, PWT, PHT>(grad, argmax, list, cnt, R, C, HW, HWs, PH_, CPW, grad_in);
 }
 
 }  // namespace frcnn
@@ -1663,20 +1889,32 @@ PxPlan px_plan(int C, int N, int H, int W, int PH, int PW, hipStream_t st, size_
     return pl;
 }
 
-template <bool HEAD>
-int px_launch(const PxPlan& pl, const float* x, const float* rois, int64_t R, int N, int C, int H, int W,
-              int PH, int PW, float ss, float* out, int32_t* argmax, const HeadArgs& hd, hipStream_t st) {
+constexpr int kF32 = FRCNN_F32, kF16 = FRCNN_F16, kBF16 = FRCNN_BF16;
+template <class T>
+constexpr bool is_f32 = std::is_same_v<T, float>;
+
+template <class T, bool HEAD>
+int px_launch(const PxPlan& pl, const T* x, const float* rois, int64_t R, int N, int C, int H, int W,
+              int PH, int PW, float ss, T* out, int32_t* argmax, const HeadArgs& hd, hipStream_t st) {
     const dim3 grid(static_cast<unsigned>(C / pl.cg), static_cast<unsigned>(pl.split), static_cast<unsigned>(N + 1));
     const bool fix7 = PH == 7 && PW == 7;
     FRCNN_REQUIRE(!pl.kps || fix7, "roi_pool_fwd: fixed-stride plan for a non-7x7 output");
-#define FRCNN_PX(CG, FX, KP)                                                                                    \
-    do {                                                                                                         \
-        if (path_cfg().roi_store)                                                                                \
-            hipLaunchKernelGGL((roi_pool_fwd_wave_kernel<1024, CG, FX, HEAD, true, KP>), grid, dim3(1024), pl.lds, \
+#define FRCNN_PX_S(CG, FX, KP, NTSV)                                                                               \
+    do {                                                                                                            \
+        if constexpr (is_f32<T>)                                                                                    \
+            hipLaunchKernelGGL((roi_pool_fwd_wave_kernel<1024, CG, FX, HEAD, NTSV, KP>), grid, dim3(1024), pl.lds,  \
                                st, x, rois, static_cast<int>(R), C, H, W, PH, PW, ss, out, argmax, pl.geo_cap, hd); \
-        else                                                                                                     \
-            hipLaunchKernelGGL((roi_pool_fwd_wave_kernel<1024, CG, FX, HEAD, false, KP>), grid, dim3(1024), pl.lds, \
-                               st, x, rois, static_cast<int>(R), C, H, W, PH, PW, ss, out, argmax, pl.geo_cap, hd); \
+        else                                                                                                        \
+            hipLaunchKernelGGL((roi_pool_fwd_wave_kernel_h<T, 1024, CG, FX, HEAD, NTSV, KP>), grid, dim3(1024),     \
+                               pl.lds, st, x, rois, static_cast<int>(R), C, H, W, PH, PW, ss, out, argmax,          \
+                               pl.geo_cap, hd);                                                                     \
+    } while (0)
+#define FRCNN_PX(CG, FX, KP)                        \
+    do {                                            \
+        if (path_cfg().roi_store)                   \
+            FRCNN_PX_S(CG, FX, KP, true);           \
+        else                                        \
+            FRCNN_PX_S(CG, FX, KP, false);          \
     } while (0)
     if (pl.cg == 16) {
         if (pl.kps) FRCNN_PX(16, 7, kFixPx * 16);
@@ -1688,6 +1926,7 @@ int px_launch(const PxPlan& pl, const float* x, const float* rois, int64_t R, in
         if (fix7) FRCNN_PX(4, 7, 0); else FRCNN_PX(4, 0, 0);
     }
 #undef FRCNN_PX
+#undef FRCNN_PX_S
     FRCNN_LAUNCH_CHECK("roi_pool_fwd_wave_kernel");
     return FRCNN_OK;
 }
@@ -1730,17 +1969,24 @@ DensePlan dense_plan(int C, int N, int H, int W, int PHW) {
     return pl;
 }
 
-template <bool HEAD, bool LIST>
-int dense_launch(const DensePlan& pl, const float* x, const float* rois, const int* list, const int* cnt,
-                 int64_t R, int N, int C, int H, int W, int PH, int PW, float ss, float* out,
+template <class T, bool HEAD, bool LIST>
+int dense_launch(const DensePlan& pl, const T* x, const float* rois, const int* list, const int* cnt,
+                 int64_t R, int N, int C, int H, int W, int PH, int PW, float ss, T* out,
                  int32_t* argmax, const HeadArgs& hd, hipStream_t st) {
     const dim3 grid(static_cast<unsigned>(C / pl.cg), static_cast<unsigned>(pl.split),
                     static_cast<unsigned>(LIST ? N : N + 1));
     const bool fix7 = PH == 7 && PW == 7;
-#define FRCNN_DENSE(CG, FX)                                                                               \
-    hipLaunchKernelGGL((roi_pool_fwd_dense_kernel<1024, CG, FX, HEAD, LIST>), grid, dim3(1024), pl.lds, st, \
-                       x, rois, list, cnt, static_cast<int>(R), C, H, W, PH, PW, ss, out, argmax, pl.cap,  \
-                       hd)
+#define FRCNN_DENSE(CG, FX)                                                                                    \
+    do {                                                                                                       \
+        if constexpr (is_f32<T>)                                                                               \
+            hipLaunchKernelGGL((roi_pool_fwd_dense_kernel<1024, CG, FX, HEAD, LIST>), grid, dim3(1024), pl.lds, \
+                               st, x, rois, list, cnt, static_cast<int>(R), C, H, W, PH, PW, ss, out, argmax,  \
+                               pl.cap, hd);                                                                    \
+        else                                                                                                   \
+            hipLaunchKernelGGL((roi_pool_fwd_dense_kernel_h<T, 1024, CG, FX, HEAD, LIST>), grid, dim3(1024),   \
+                               pl.lds, st, x, rois, list, cnt, static_cast<int>(R), C, H, W, PH, PW, ss, out,  \
+                               argmax, pl.cap, hd);                                                            \
+    } while (0)
     if (pl.cg == 16) {
         if (fix7) FRCNN_DENSE(16, 7); else FRCNN_DENSE(16, 0);
     } else if (pl.cg == 8) {
@@ -1780,15 +2026,24 @@ FwdChoice choose_fwd(int N, int C, int H, int W, int PH, int PW, bool sorted, hi
     return ch;
 }
 
-template <bool HEAD>
-int fwd_tile_launch(const FwdChoice& ch, const float* x, const float* rois, int64_t R, int N, int C, int H, int W,
-                    int PH, int PW, float ss, float* out, int32_t* argmax, const HeadArgs& hd, hipStream_t st) {
+template <class T, bool HEAD>
+int fwd_tile_launch(const FwdChoice& ch, const T* x, const float* rois, int64_t R, int N, int C, int H, int W,
+                    int PH, int PW, float ss, T* out, int32_t* argmax, const HeadArgs& hd, hipStream_t st) {
     switch (ch.kind) {
-        case kFwdWave: return px_launch<HEAD>(ch.px, x, rois, R, N, C, H, W, PH, PW, ss, out, argmax, hd, st);
+        case kFwdWave: return px_launch<T, HEAD>(ch.px, x, rois, R, N, C, H, W, PH, PW, ss, out, argmax, hd, st);
         default:
-            return dense_launch<HEAD, false>(ch.dn, x, rois, nullptr, nullptr, R, N, C, H, W, PH, PW, ss, out,
-                                             argmax, hd, st);
+            return dense_launch<T, HEAD, false>(ch.dn, x, rois, nullptr, nullptr, R, N, C, H, W, PH, PW, ss, out,
+                                                argmax, hd, st);
     }
+}
+
+// The element type's name as the demangled kernel names spell it.
+const char* elem_name(int dtype) { return dtype == kF16 ? "__half" : "__hip_bfloat16"; }
+
+// `kernel<args>` for fp32, `kernel_h<T, args>` for a 16-bit element type.
+int typed_kernel_name(char* name, size_t len, int dtype, const char* kernel, const char* args) {
+    return dtype == kF32 ? snprintf(name, len, "%s<%s>", kernel, args)
+                         : snprintf(name, len, "%s_h<%s, %s>", kernel, elem_name(dtype), args);
 }
 }  // namespace
 
@@ -1797,10 +2052,11 @@ extern "C" size_t frcnn_roi_pool_fwd_workspace_size(int64_t R, int N, int C) {
     return carve_fwd(nullptr, R, N).bytes;
 }
 
-extern "C" int frcnn_roi_pool_fwd(const float* x, const float* rois, int64_t R, int N, int C,
-                                  int H, int W, int PH, int PW, float spatial_scale,
-                                  int rois_sorted, float* out, int32_t* argmax, void* workspace,
-                                  size_t ws_bytes, void* stream) {
+namespace {
+template <class T>
+int roi_pool_fwd_impl(const T* x, const float* rois, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                      float spatial_scale, int rois_sorted, T* out, int32_t* argmax, void* workspace,
+                      size_t ws_bytes, void* stream) {
     FRCNN_REQUIRE(R >= 0 && N >= 0 && C >= 0 && H >= 0 && W >= 0, "frcnn_roi_pool_fwd: bad shape");
     FRCNN_REQUIRE(PH > 0 && PW > 0 && PH * PW <= kMaxBins,
                   "frcnn_roi_pool_fwd: output_size must have 1..%d bins", kMaxBins);
@@ -1816,28 +2072,68 @@ extern "C" int frcnn_roi_pool_fwd(const float* x, const float* rois, int64_t R, 
         hipLaunchKernelGGL(roi_lists_kernel, dim3(N + 1), dim3(1024), 0, st, rois, static_cast<int>(R), N,
                            w.list, w.cnt);
         FRCNN_LAUNCH_CHECK("roi_lists_kernel");
-        int rc = dense_launch<false, true>(ch.dn, x, rois, w.list, w.cnt, R, N, C, H, W, PH, PW, spatial_scale,
-                                           out, argmax, HeadArgs{}, st);
+        int rc = dense_launch<T, false, true>(ch.dn, x, rois, w.list, w.cnt, R, N, C, H, W, PH, PW, spatial_scale,
+                                              out, argmax, HeadArgs{}, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(roi_pool_invalid_fill_kernel, dim3(64), dim3(256), 0, st, w.list, w.cnt,
-                           static_cast<int>(R), N, static_cast<size_t>(C) * PH * PW, out, argmax);
+        if constexpr (is_f32<T>)
+            hipLaunchKernelGGL(roi_pool_invalid_fill_kernel, dim3(64), dim3(256), 0, st, w.list, w.cnt,
+                               static_cast<int>(R), N, static_cast<size_t>(C) * PH * PW, out, argmax);
+        else
+            hipLaunchKernelGGL(roi_pool_invalid_fill_kernel_h<T>, dim3(64), dim3(256), 0, st, w.list, w.cnt,
+                               static_cast<int>(R), N, static_cast<size_t>(C) * PH * PW, out, argmax,
+                               static_cast<const float*>(nullptr), HeadArgs{});
         FRCNN_LAUNCH_CHECK("roi_pool_invalid_fill_kernel");
         return FRCNN_OK;
     }
     if (ch.kind != kFwdGeneric)
-        return fwd_tile_launch<false>(ch, x, rois, R, N, C, H, W, PH, PW, spatial_scale, out, argmax, HeadArgs{}, st);
+        return fwd_tile_launch<T, false>(ch, x, rois, R, N, C, H, W, PH, PW, spatial_scale, out, argmax, HeadArgs{},
+                                         st);
     // generic path: one workgroup per RoI, gathers from L1/L2
     const size_t total = static_cast<size_t>(C) * PH * PW;
     const bool aligned = (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
                          (reinterpret_cast<uintptr_t>(argmax) % 16 == 0);
+#define FRCNN_GENERIC(VEC)                                                                                  \
+    do {                                                                                                    \
+        if constexpr (is_f32<T>)                                                                            \
+            hipLaunchKernelGGL(roi_pool_fwd_kernel<VEC>, dim3(static_cast<unsigned>(R)), dim3(256), 0, st, x, \
+                               rois, N, C, H, W, PH, PW, spatial_scale, out, argmax);                       \
+        else                                                                                                \
+            hipLaunchKernelGGL((roi_pool_fwd_kernel_h<T, VEC>), dim3(static_cast<unsigned>(R)), dim3(256), 0, \
+                               st, x, rois, N, C, H, W, PH, PW, spatial_scale, out, argmax);                \
+    } while (0)
     if (total % 4 == 0 && aligned)
-        hipLaunchKernelGGL(roi_pool_fwd_kernel<true>, dim3(static_cast<unsigned>(R)), dim3(256), 0,
-                           st, x, rois, N, C, H, W, PH, PW, spatial_scale, out, argmax);
+        FRCNN_GENERIC(true);
     else
-        hipLaunchKernelGGL(roi_pool_fwd_kernel<false>, dim3(static_cast<unsigned>(R)), dim3(256), 0,
-                           st, x, rois, N, C, H, W, PH, PW, spatial_scale, out, argmax);
+        FRCNN_GENERIC(false);
+#undef FRCNN_GENERIC
     FRCNN_LAUNCH_CHECK("roi_pool_fwd_kernel");
     return FRCNN_OK;
+}
+}  // namespace
+
+extern "C" int frcnn_roi_pool_fwd(const float* x, const float* rois, int64_t R, int N, int C,
+                                  int H, int W, int PH, int PW, float spatial_scale,
+                                  int rois_sorted, float* out, int32_t* argmax, void* workspace,
+                                  size_t ws_bytes, void* stream) {
+    return roi_pool_fwd_impl<float>(x, rois, R, N, C, H, W, PH, PW, spatial_scale, rois_sorted, out, argmax,
+                                    workspace, ws_bytes, stream);
+}
+
+extern "C" int frcnn_roi_pool_fwd_t(int dtype, const void* x, const float* rois, int64_t R, int N, int C,
+                                    int H, int W, int PH, int PW, float spatial_scale,
+                                    int rois_sorted, void* out, int32_t* argmax, void* workspace,
+                                    size_t ws_bytes, void* stream) {
+    FRCNN_REQUIRE(dtype == kF32 || dtype == kF16 || dtype == kBF16,
+                  "frcnn_roi_pool_fwd_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16", dtype);
+    if (dtype == kF16)
+        return roi_pool_fwd_impl(static_cast<const __half*>(x), rois, R, N, C, H, W, PH, PW, spatial_scale,
+                                 rois_sorted, static_cast<__half*>(out), argmax, workspace, ws_bytes, stream);
+    if (dtype == kBF16)
+        return roi_pool_fwd_impl(static_cast<const __hip_bfloat16*>(x), rois, R, N, C, H, W, PH, PW, spatial_scale,
+                                 rois_sorted, static_cast<__hip_bfloat16*>(out), argmax, workspace, ws_bytes,
+                                 stream);
+    return roi_pool_fwd_impl(static_cast<const float*>(x), rois, R, N, C, H, W, PH, PW, spatial_scale, rois_sorted,
+                             static_cast<float*>(out), argmax, workspace, ws_bytes, stream);
 }
 
 // head != 0 names the launch of frcnn_roi_pool_fwd_head for 16-B aligned [R,4]
@@ -1845,6 +2141,13 @@ extern "C" int frcnn_roi_pool_fwd(const float* x, const float* rois, int64_t R, 
 // head == 0 launch.
 extern "C" int frcnn_roi_pool_fwd_kernel(int64_t R, int N, int C, int H, int W, int PH, int PW, int rois_sorted,
                                          int head, void* stream, char* name, size_t len) {
+    return frcnn_roi_pool_fwd_kernel_t(FRCNN_F32, R, N, C, H, W, PH, PW, rois_sorted, head, stream, name, len);
+}
+
+extern "C" int frcnn_roi_pool_fwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                           int rois_sorted, int head, void* stream, char* name, size_t len) {
+    FRCNN_REQUIRE(dtype == kF32 || dtype == kF16 || dtype == kBF16,
+                  "frcnn_roi_pool_fwd_kernel_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16", dtype);
     FRCNN_REQUIRE(name && len > 0, "frcnn_roi_pool_fwd_kernel: null name");
     FRCNN_REQUIRE(R >= 0 && N >= 0 && C >= 0 && H >= 0 && W >= 0 && PH > 0 && PW > 0,
                   "frcnn_roi_pool_fwd_kernel: bad shape");
@@ -1854,33 +2157,37 @@ extern "C" int frcnn_roi_pool_fwd_kernel(int64_t R, int N, int C, int H, int W, 
     // plain forward, like the dense-list / generic choices below
     const char* hb = head == 1 ? "true" : "false";
     int n = 0;
+    char args[96];
     switch (ch.kind) {
         case kFwdWave:
             if (ch.px.kps)  // kps implies the 7x7 head (px_plan)
-                n = snprintf(name, len, "roi_pool_fwd_wave_kernel<1024, %d, %d, %s, %s, %d>", ch.px.cg, fx, hb,
-                             path_cfg().roi_store ? "true" : "false", kFixPx * 16);
+                snprintf(args, sizeof(args), "1024, %d, %d, %s, %s, %d", ch.px.cg, fx, hb,
+                         path_cfg().roi_store ? "true" : "false", kFixPx * 16);
             else
-                n = snprintf(name, len, "roi_pool_fwd_wave_kernel<1024, %d, %d, %s%s>", ch.px.cg, fx, hb,
-                             path_cfg().roi_store ? ", true" : "");
+                snprintf(args, sizeof(args), "1024, %d, %d, %s%s", ch.px.cg, fx, hb,
+                         path_cfg().roi_store ? ", true" : "");
+            n = typed_kernel_name(name, len, dtype, "roi_pool_fwd_wave_kernel", args);
             break;
         case kFwdDense:
-            n = snprintf(name, len, "roi_pool_fwd_dense_kernel<1024, %d, %d, %s, false>", ch.dn.cg, fx, hb);
+            snprintf(args, sizeof(args), "1024, %d, %d, %s, false", ch.dn.cg, fx, hb);
+            n = typed_kernel_name(name, len, dtype, "roi_pool_fwd_dense_kernel", args);
             break;
         case kFwdDenseList:
-            n = snprintf(name, len, "roi_pool_fwd_dense_kernel<1024, %d, %d, false, true>", ch.dn.cg, fx);
+            snprintf(args, sizeof(args), "1024, %d, %d, false, true", ch.dn.cg, fx);
+            n = typed_kernel_name(name, len, dtype, "roi_pool_fwd_dense_kernel", args);
             break;
         default:
-            n = snprintf(name, len, "roi_pool_fwd_kernel<%s>",
-                         (static_cast<size_t>(C) * PH * PW) % 4 == 0 ? "true" : "false");
+            n = typed_kernel_name(name, len, dtype, "roi_pool_fwd_kernel",
+                                  (static_cast<size_t>(C) * PH * PW) % 4 == 0 ? "true" : "false");
     }
     return n < 0 ? FRCNN_EINVAL : FRCNN_OK;
 }
 
-extern "C" int frcnn_roi_pool_fwd_head(const float* x, const float* rois, const float* roi_inds,
-                                       int64_t R, int N, int C, int H, int W, int PH, int PW,
-                                       float img_h, float img_w, float spatial_scale,
-                                       int rois_sorted, float* boxes, float* out, int32_t* argmax,
-                                       void* workspace, size_t ws_bytes, void* stream) {
+namespace {
+template <class T>
+int roi_pool_fwd_head_impl(const T* x, const float* rois, const float* roi_inds, int64_t R, int N, int C, int H,
+                           int W, int PH, int PW, float img_h, float img_w, float spatial_scale, int rois_sorted,
+                           float* boxes, T* out, int32_t* argmax, void* workspace, size_t ws_bytes, void* stream) {
     FRCNN_REQUIRE(R >= 0 && N >= 0 && C >= 0 && H >= 0 && W >= 0, "frcnn_roi_pool_fwd_head: bad shape");
     FRCNN_REQUIRE(PH > 0 && PW > 0 && PH * PW <= kMaxBins,
                   "frcnn_roi_pool_fwd_head: output_size must have 1..%d bins", kMaxBins);
@@ -1893,14 +2200,44 @@ extern "C" int frcnn_roi_pool_fwd_head(const float* x, const float* rois, const 
         int rc = frcnn_roi_transform(rois, roi_inds, R, img_h, img_w, H, W, boxes, stream);
         if (rc != FRCNN_OK) return rc;
         if (C == 0) return FRCNN_OK;
-        return frcnn_roi_pool_fwd(x, boxes, R, N, C, H, W, PH, PW, spatial_scale, rois_sorted, out,
-                                  argmax, workspace, ws_bytes, stream);
+        return roi_pool_fwd_impl<T>(x, boxes, R, N, C, H, W, PH, PW, spatial_scale, rois_sorted, out, argmax,
+                                    workspace, ws_bytes, stream);
     }
     // transform + pack inside the pool kernel
     FRCNN_REQUIRE(x && out && argmax, "frcnn_roi_pool_fwd_head: null pointer");
     const HeadArgs hd{roi_inds, img_h, img_w, static_cast<float>(H), static_cast<float>(W), boxes};
-    return fwd_tile_launch<true>(ch, x, rois, R, N, C, H, W, PH, PW, spatial_scale, out, argmax, hd,
-                                 as_stream(stream));
+    return fwd_tile_launch<T, true>(ch, x, rois, R, N, C, H, W, PH, PW, spatial_scale, out, argmax, hd,
+                                    as_stream(stream));
+}
+}  // namespace
+
+extern "C" int frcnn_roi_pool_fwd_head(const float* x, const float* rois, const float* roi_inds,
+                                       int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                       float img_h, float img_w, float spatial_scale,
+                                       int rois_sorted, float* boxes, float* out, int32_t* argmax,
+                                       void* workspace, size_t ws_bytes, void* stream) {
+    return roi_pool_fwd_head_impl<float>(x, rois, roi_inds, R, N, C, H, W, PH, PW, img_h, img_w, spatial_scale,
+                                         rois_sorted, boxes, out, argmax, workspace, ws_bytes, stream);
+}
+
+extern "C" int frcnn_roi_pool_fwd_head_t(int dtype, const void* x, const float* rois, const float* roi_inds,
+                                         int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                         float img_h, float img_w, float spatial_scale,
+                                         int rois_sorted, float* boxes, void* out, int32_t* argmax,
+                                         void* workspace, size_t ws_bytes, void* stream) {
+    FRCNN_REQUIRE(dtype == kF32 || dtype == kF16 || dtype == kBF16,
+                  "frcnn_roi_pool_fwd_head_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16", dtype);
+    if (dtype == kF16)
+        return roi_pool_fwd_head_impl(static_cast<const __half*>(x), rois, roi_inds, R, N, C, H, W, PH, PW, img_h,
+                                      img_w, spatial_scale, rois_sorted, boxes, static_cast<__half*>(out), argmax,
+                                      workspace, ws_bytes, stream);
+    if (dtype == kBF16)
+        return roi_pool_fwd_head_impl(static_cast<const __hip_bfloat16*>(x), rois, roi_inds, R, N, C, H, W, PH, PW,
+                                      img_h, img_w, spatial_scale, rois_sorted, boxes,
+                                      static_cast<__hip_bfloat16*>(out), argmax, workspace, ws_bytes, stream);
+    return roi_pool_fwd_head_impl(static_cast<const float*>(x), rois, roi_inds, R, N, C, H, W, PH, PW, img_h, img_w,
+                                  spatial_scale, rois_sorted, boxes, static_cast<float*>(out), argmax, workspace,
+                                  ws_bytes, stream);
 }
 
 namespace {
@@ -1975,25 +2312,38 @@ BwdPlan bwd_plan(int64_t R, int N, int C, int H, int W, int PH, int PW) {
 
 extern "C" int frcnn_roi_pool_bwd_kernel(int64_t R, int N, int C, int H, int W, int PH, int PW, char* name,
                                          size_t len) {
+    return frcnn_roi_pool_bwd_kernel_t(FRCNN_F32, R, N, C, H, W, PH, PW, name, len);
+}
+
+extern "C" int frcnn_roi_pool_bwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                           char* name, size_t len) {
+    FRCNN_REQUIRE(dtype == kF32 || dtype == kF16 || dtype == kBF16,
+                  "frcnn_roi_pool_bwd_kernel_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16", dtype);
     FRCNN_REQUIRE(name && len > 0, "frcnn_roi_pool_bwd_kernel: null name");
     FRCNN_REQUIRE(R >= 0 && N >= 0 && C >= 0 && H >= 0 && W >= 0 && PH > 0 && PW > 0,
                   "frcnn_roi_pool_bwd_kernel: bad shape");
     const BwdPlan pl = bwd_plan(R, N, C, H, W, PH, PW);
     const size_t plane_bytes = static_cast<size_t>(H) * W * sizeof(float);
     int n;
-    if (pl.lead)
-        n = snprintf(name, len, "roi_pool_bwd_lead_kernel<%d, 7, %d>", kBwdLead, PH == 7 ? 7 : 0);
-    else if (pl.ring)
-        n = snprintf(name, len, "roi_pool_bwd_pf_kernel<%d>", kBwdRing);
-    else
-        n = snprintf(name, len, "roi_pool_bwd_kernel<%s>", plane_bytes <= kPlaneBudget ? "true" : "false");
+    char args[32];
+    if (pl.lead) {
+        snprintf(args, sizeof(args), "%d, 7, %d", kBwdLead, PH == 7 ? 7 : 0);
+        n = typed_kernel_name(name, len, dtype, "roi_pool_bwd_lead_kernel", args);
+    } else if (pl.ring) {
+        snprintf(args, sizeof(args), "%d", kBwdRing);
+        n = typed_kernel_name(name, len, dtype, "roi_pool_bwd_pf_kernel", args);
+    } else {
+        n = typed_kernel_name(name, len, dtype, "roi_pool_bwd_kernel",
+                              plane_bytes <= kPlaneBudget ? "true" : "false");
+    }
     return n < 0 ? FRCNN_EINVAL : FRCNN_OK;
 }
 
-extern "C" int frcnn_roi_pool_bwd(const float* grad, const float* rois, const int32_t* argmax,
-                                  int64_t R, int N, int C, int H, int W, int PH, int PW,
-                                  float spatial_scale, float* grad_in, void* workspace,
-                                  size_t ws_bytes, void* stream) {
+namespace {
+template <class T>
+int roi_pool_bwd_impl(const T* grad, const float* rois, const int32_t* argmax, int64_t R, int N, int C, int H,
+                      int W, int PH, int PW, float spatial_scale, T* grad_in, void* workspace, size_t ws_bytes,
+                      void* stream) {
     FRCNN_REQUIRE(R >= 0 && N >= 0 && C >= 0 && H >= 0 && W >= 0, "frcnn_roi_pool_bwd: bad shape");
     FRCNN_REQUIRE(PH > 0 && PW > 0 && PH * PW <= kMaxBins, "frcnn_roi_pool_bwd: bad output_size");
     FRCNN_REQUIRE(R <= 0x7fffffff, "frcnn_roi_pool_bwd: too many rois");
@@ -2002,7 +2352,7 @@ extern "C" int frcnn_roi_pool_bwd(const float* grad, const float* rois, const in
     if (N == 0 || C == 0 || HW == 0) return FRCNN_OK;
     FRCNN_REQUIRE(grad_in, "frcnn_roi_pool_bwd: null grad_in");
     if (R == 0) {
-        if (hipMemsetAsync(grad_in, 0, sizeof(float) * N * C * HW, st) != hipSuccess)
+        if (hipMemsetAsync(grad_in, 0, sizeof(T) * N * C * HW, st) != hipSuccess)
             return check_launch("frcnn_roi_pool_bwd memset");
         return FRCNN_OK;
     }
@@ -2038,34 +2388,93 @@ extern "C" int frcnn_roi_pool_bwd(const float* grad, const float* rois, const in
         dim3 grid((C + icpw - 1) / icpw, N);
         if (lead)
         {
+#define FRCNN_LEAD(PHT)                                                                                          \
+    do {                                                                                                         \
+        if constexpr (is_f32<T>)                                                                                 \
+            hipLaunchKernelGGL((roi_pool_bwd_lead_kernel<kBwdLead, 7, PHT>), grid, dim3(64 * icpw), lead_bytes,   \
+                               st, grad, argmax, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),    \
+                               HWs, PH, icpw, grad_in);                                                          \
+        else                                                                                                     \
+            hipLaunchKernelGGL((roi_pool_bwd_lead_kernel_h<T, kBwdLead, 7, PHT>), grid, dim3(64 * icpw),          \
+                               lead_bytes, st, grad, argmax, w.list, w.cnt, static_cast<int>(R), C,              \
+                               static_cast<int>(HW), HWs, PH, icpw, grad_in);                                    \
+    } while (0)
             if (PH == 7)
-                hipLaunchKernelGGL((roi_pool_bwd_lead_kernel<kBwdLead, 7, 7>), grid, dim3(64 * icpw), lead_bytes,
-                                   st, grad, argmax, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),
-                                   HWs, PH, icpw, grad_in);
+                FRCNN_LEAD(7);
             else
-                hipLaunchKernelGGL((roi_pool_bwd_lead_kernel<kBwdLead, 7, 0>), grid, dim3(64 * icpw), lead_bytes,
-                                   st, grad, argmax, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),
-                                   HWs, PH, icpw, grad_in);
+                FRCNN_LEAD(0);
+#undef FRCNN_LEAD
         }
-        else
+        else if constexpr (is_f32<T>)
             hipLaunchKernelGGL(roi_pool_bwd_pf_kernel<kBwdRing>, grid, dim3(64 * icpw), icpw * plane_bytes, st,
                                grad, argmax, w.cmask, w.code, w.list, w.cnt, static_cast<int>(R), C,
+                               static_cast<int>(HW), PHW, PW, icpw, grad_in);
+        else
+            hipLaunchKernelGGL((roi_pool_bwd_pf_kernel_h<T, kBwdRing>), grid, dim3(64 * icpw), icpw * plane_bytes,
+                               st, grad, argmax, w.cmask, w.code, w.list, w.cnt, static_cast<int>(R), C,
                                static_cast<int>(HW), PHW, PW, icpw, grad_in);
     } else if (plane_bytes <= kPlaneBudget) {
         int cpw = static_cast<int>(kPlaneBudget / plane_bytes);
         cpw = cpw > 16 ? 16 : cpw;
         cpw = cpw > C ? C : cpw;
         dim3 grid((C + cpw - 1) / cpw, N);
-        hipLaunchKernelGGL(roi_pool_bwd_kernel<true>, grid, dim3(64 * cpw), cpw * plane_bytes, st,
-                           grad, argmax, w.cmask, w.list, w.cnt, static_cast<int>(R), C,
-                           static_cast<int>(HW), PHW, cpw, grad_in);
+        if constexpr (is_f32<T>)
+            hipLaunchKernelGGL(roi_pool_bwd_kernel<true>, grid, dim3(64 * cpw), cpw * plane_bytes, st,
+                               grad, argmax, w.cmask, w.list, w.cnt, static_cast<int>(R), C,
+                               static_cast<int>(HW), PHW, cpw, grad_in);
+        else
+            hipLaunchKernelGGL((roi_pool_bwd_kernel_h<T, true>), grid, dim3(64 * cpw), cpw * plane_bytes, st,
+                               grad, argmax, w.cmask, w.list, w.cnt, static_cast<int>(R), C,
+                               static_cast<int>(HW), PHW, cpw, grad_in, static_cast<float*>(nullptr));
     } else {
         const int cpw = 4;
         dim3 grid((C + cpw - 1) / cpw, N);
-        hipLaunchKernelGGL(roi_pool_bwd_kernel<false>, grid, dim3(64 * cpw), 0, st, grad, argmax,
-                           w.cmask, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),
-                           PHW, cpw, grad_in);
+        if constexpr (is_f32<T>) {
+            hipLaunchKernelGGL(roi_pool_bwd_kernel<false>, grid, dim3(64 * cpw), 0, st, grad, argmax,
+                               w.cmask, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),
+                               PHW, cpw, grad_in);
+        } else {
+            // Planes too large for LDS are summed in global memory, which for a 16-bit
+            // grad_in cannot be grad_in itself: this one path takes an [N,C,H,W] fp32
+            // scratch of its own from the stream-ordered allocator (no host sync; it is
+            // not part of the workspace, whose size does not depend on C, H or W) and
+            // returns it behind the kernel.
+            float* fplanes = nullptr;
+            if (hipMallocAsync(reinterpret_cast<void**>(&fplanes), sizeof(float) * N * C * HW, st) != hipSuccess)
+                return check_launch("frcnn_roi_pool_bwd scratch planes");
+            hipLaunchKernelGGL((roi_pool_bwd_kernel_h<T, false>), grid, dim3(64 * cpw), 0, st, grad, argmax,
+                               w.cmask, w.list, w.cnt, static_cast<int>(R), C, static_cast<int>(HW),
+                               PHW, cpw, grad_in, fplanes);
+            const int rc = check_launch("roi_pool_bwd_kernel");
+            (void)hipFreeAsync(fplanes, st);
+            return rc;
+        }
     }
     FRCNN_LAUNCH_CHECK("roi_pool_bwd_kernel");
     return FRCNN_OK;
+}
+}  // namespace
+
+extern "C" int frcnn_roi_pool_bwd(const float* grad, const float* rois, const int32_t* argmax,
+                                  int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                  float spatial_scale, float* grad_in, void* workspace,
+                                  size_t ws_bytes, void* stream) {
+    return roi_pool_bwd_impl<float>(grad, rois, argmax, R, N, C, H, W, PH, PW, spatial_scale, grad_in, workspace,
+                                    ws_bytes, stream);
+}
+
+extern "C" int frcnn_roi_pool_bwd_t(int dtype, const void* grad, const float* rois, const int32_t* argmax,
+                                    int64_t R, int N, int C, int H, int W, int PH, int PW,
+                                    float spatial_scale, void* grad_in, void* workspace,
+                                    size_t ws_bytes, void* stream) {
+    FRCNN_REQUIRE(dtype == kF32 || dtype == kF16 || dtype == kBF16,
+                  "frcnn_roi_pool_bwd_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16", dtype);
+    if (dtype == kF16)
+        return roi_pool_bwd_impl(static_cast<const __half*>(grad), rois, argmax, R, N, C, H, W, PH, PW,
+                                 spatial_scale, static_cast<__half*>(grad_in), workspace, ws_bytes, stream);
+    if (dtype == kBF16)
+        return roi_pool_bwd_impl(static_cast<const __hip_bfloat16*>(grad), rois, argmax, R, N, C, H, W, PH, PW,
+                                 spatial_scale, static_cast<__hip_bfloat16*>(grad_in), workspace, ws_bytes, stream);
+    return roi_pool_bwd_impl(static_cast<const float*>(grad), rois, argmax, R, N, C, H, W, PH, PW, spatial_scale,
+                             static_cast<float*>(grad_in), workspace, ws_bytes, stream);
 }

@@ -5,6 +5,10 @@ RoI transform + ``[idx, box]`` pack (nets/heads.py:42-47) and RoIPool forward
 (nets/heads.py:48) are one HIP launch (``ops.roi_pool_head``) when the RoIs
 are grouped by image, with roi_pool's HIP backward; the classifier (layer4 +
 avgpool) and the two FCs stay plain PyTorch (not the target).
+
+float16 / bfloat16 features (a backbone under ``torch.autocast``) are pooled
+in their own type: ``cropped`` reaches the classifier in ``x``'s dtype and
+``x.grad`` comes back in it, with no widening cast on either side.
 """
 from __future__ import annotations
 

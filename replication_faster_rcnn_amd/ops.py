@@ -29,6 +29,12 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   CPU (reference style), be strided views or another float type; they are moved
   to the current HIP device as contiguous fp32, and results are returned on the
   input's device.  They raise only on shapes that do not belong together.
+  One exception keeps its type: a float16 or bfloat16 ``input`` of ``roi_pool``,
+  ``roi_pool_with_argmax`` and ``roi_pool_head`` (a backbone under autocast) is
+  moved or made contiguous if needed but never widened, the pooled output and
+  the gradient have the input's dtype as torchvision's do, and the kernels
+  read and write the 16-bit values directly (DESIGN.md §3 "RoIPool in 16-bit
+  types").  ``boxes`` / ``rois`` / ``roi_inds`` stay fp32, ``argmax`` int32.
 * The hot-path ops on device tensors (``propose``, ``roi_transform``,
   ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
@@ -86,17 +92,35 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torc
 
 
 # ------------------------------------------------------------------ roi_pool
+_POOL_HALF = (torch.float16, torch.bfloat16)
+_POOL_DTYPE_CODE = _lib.DTYPE_CODES  # torch dtype -> the C-ABI's FRCNN_F32 / FRCNN_F16 / FRCNN_BF16
+
+
+def _pool_input(t: torch.Tensor) -> torch.Tensor:
+    """RoIPool's feature rule: float16 / bfloat16 keep their type (moved or made
+    contiguous if needed, never widened), everything else becomes fp32."""
+    return _to_dev(t, t.dtype if t.dtype in _POOL_HALF else torch.float32)
+
+
+def _pool_dtype_error(op: str, dtype):
+    return RuntimeError(f"{op}: tensors must be float32, float16 or bfloat16; got {dtype}")
+
+
 def _roi_pool_fwd(x: torch.Tensor, rois: torch.Tensor, ph: int, pw: int, ss: float,
                   rois_sorted: bool = False):
     lib = _lib.load()
     N, C, H, W = x.shape
     R = rois.size(0)
-    out = torch.empty((R, C, ph, pw), dtype=torch.float32, device=x.device)
+    dt = x.dtype
+    code = _POOL_DTYPE_CODE.get(dt)
+    if code is None:
+        raise _pool_dtype_error("roi_pool forward", dt)
+    out = torch.empty((R, C, ph, pw), dtype=dt, device=x.device)
     am = torch.empty((R, C, ph, pw), dtype=torch.int32, device=x.device)
     ws = _lib.cached_workspace("roi_pool_fwd", lib.frcnn_roi_pool_fwd_workspace_size(R, N, C), x.device)
-    _lib.check(lib.frcnn_roi_pool_fwd(_lib.ptr(x), _lib.ptr(rois), R, N, C, H, W, ph, pw, float(ss),
-                                      int(bool(rois_sorted)), _lib.ptr(out), _lib.ptr(am),
-                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "roi_pool forward")
+    _lib.check(lib.frcnn_roi_pool_fwd_t(code, _lib.ptr(x), _lib.ptr(rois), R, N, C, H, W,
+                                        ph, pw, float(ss), int(bool(rois_sorted)), _lib.ptr(out), _lib.ptr(am),
+                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "roi_pool forward")
     return out, am
 
 
@@ -114,13 +138,24 @@ def _roi_pool_bwd(grad: torch.Tensor, rois: torch.Tensor, am: torch.Tensor, shap
     lib = _lib.load()
     N, C, H, W = shape
     R, _, ph, pw = grad.shape
-    gi = torch.empty((N, C, H, W), dtype=torch.float32, device=grad.device)
+    dt = grad.dtype
+    code = _POOL_DTYPE_CODE.get(dt)
+    if code is None:
+        raise _pool_dtype_error("roi_pool backward", dt)
+    gi = torch.empty((N, C, H, W), dtype=dt, device=grad.device)
     ws = _lib.cached_workspace("roi_pool_bwd", lib.frcnn_roi_pool_bwd_workspace_size(R, N, ph, pw),
                                grad.device)
-    _lib.check(lib.frcnn_roi_pool_bwd(_lib.ptr(grad), _lib.ptr(rois), _lib.ptr(am), R, N, C, H, W,
-                                      ph, pw, float(ss), _lib.ptr(gi), _lib.ptr(ws), ws.numel(),
-                                      _lib.stream_ptr()), "roi_pool backward")
+    _lib.check(lib.frcnn_roi_pool_bwd_t(code, _lib.ptr(grad), _lib.ptr(rois), _lib.ptr(am),
+                                        R, N, C, H, W, ph, pw, float(ss), _lib.ptr(gi), _lib.ptr(ws), ws.numel(),
+                                        _lib.stream_ptr()), "roi_pool backward")
     return gi
+
+
+def _pool_grad(grad_out: torch.Tensor, dtype) -> torch.Tensor:
+    """The gradient as the backward kernel reads it: contiguous, in the pooled
+    output's dtype (which autograd already guarantees; the cast is a no-op then)."""
+    g = grad_out if grad_out.dtype == dtype else grad_out.to(dtype)
+    return g.contiguous()
 
 
 class _RoIPoolFunction(torch.autograd.Function):
@@ -128,15 +163,15 @@ class _RoIPoolFunction(torch.autograd.Function):
     def forward(ctx, x, rois, ph, pw, ss, rois_sorted=False):
         out, am = _roi_pool_fwd(x, rois, ph, pw, ss, rois_sorted)
         ctx.save_for_backward(rois, am)
-        ctx.meta = (tuple(x.shape), ss)
+        ctx.meta = (tuple(x.shape), ss, x.dtype)
         ctx.mark_non_differentiable(am)
         return out, am
 
     @staticmethod
     def backward(ctx, grad_out, _grad_am):
         rois, am = ctx.saved_tensors
-        shape, ss = ctx.meta
-        gi = _roi_pool_bwd(grad_out.contiguous().float(), rois, am, shape, ss)
+        shape, ss, dtype = ctx.meta
+        gi = _roi_pool_bwd(_pool_grad(grad_out, dtype), rois, am, shape, ss)
         return gi, None, None, None, None, None
 
 
@@ -144,20 +179,25 @@ def _roi_pool_head_fwd(x, rois, roi_inds, ph, pw, img_h, img_w, ss, rois_sorted,
     lib = _lib.load()
     N, C, H, W = x.shape
     R = rois.size(0)
+    dt = x.dtype
+    code = _POOL_DTYPE_CODE.get(dt)
+    if code is None:
+        raise _pool_dtype_error("roi_pool_head", dt)
     if outs is None:
         boxes = torch.empty((R, 5), dtype=torch.float32, device=x.device)
-        out = torch.empty((R, C, ph, pw), dtype=torch.float32, device=x.device)
+        out = torch.empty((R, C, ph, pw), dtype=dt, device=x.device)
         am = torch.empty((R, C, ph, pw), dtype=torch.int32, device=x.device)
     else:  # caller-owned (out, argmax, boxes): no allocation on the issue path
         out, am, boxes = outs
         if (tuple(out.shape) != (R, C, ph, pw) or tuple(am.shape) != (R, C, ph, pw)
-                or tuple(boxes.shape) != (R, 5) or out.dtype != torch.float32
+                or tuple(boxes.shape) != (R, 5) or out.dtype != dt
                 or am.dtype != torch.int32 or boxes.dtype != torch.float32):
-            raise RuntimeError("roi_pool_head: out buffers must be fp32 [R,C,ph,pw], int32 [R,C,ph,pw], "
+            what = "fp32" if dt == torch.float32 else f"{dt} (the input's dtype)"
+            raise RuntimeError(f"roi_pool_head: out buffers must be {what} [R,C,ph,pw], int32 [R,C,ph,pw], "
                                "fp32 [R,5]")
     ws = _lib.cached_workspace("roi_pool_fwd", lib.frcnn_roi_pool_fwd_workspace_size(R, N, C), x.device)
-    _lib.check(lib.frcnn_roi_pool_fwd_head(
-        _lib.ptr(x), _lib.ptr(rois), _lib.ptr(roi_inds), R, N, C, H, W, ph, pw, float(img_h),
+    _lib.check(lib.frcnn_roi_pool_fwd_head_t(
+        code, _lib.ptr(x), _lib.ptr(rois), _lib.ptr(roi_inds), R, N, C, H, W, ph, pw, float(img_h),
         float(img_w), float(ss), int(bool(rois_sorted)), _lib.ptr(boxes), _lib.ptr(out),
         _lib.ptr(am), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "roi_pool_head forward")
     return out, am, boxes
@@ -171,15 +211,15 @@ class _RoIPoolHeadFunction(torch.autograd.Function):
     def forward(ctx, x, rois, roi_inds, ph, pw, img_h, img_w, ss, rois_sorted):
         out, am, boxes = _roi_pool_head_fwd(x, rois, roi_inds, ph, pw, img_h, img_w, ss, rois_sorted)
         ctx.save_for_backward(boxes, am)
-        ctx.meta = (tuple(x.shape), ss)
+        ctx.meta = (tuple(x.shape), ss, x.dtype)
         ctx.mark_non_differentiable(am, boxes)
         return out, am, boxes
 
     @staticmethod
     def backward(ctx, grad_out, _grad_am, _grad_boxes):
         boxes, am = ctx.saved_tensors
-        shape, ss = ctx.meta
-        gi = _roi_pool_bwd(grad_out.contiguous().float(), boxes, am, shape, ss)
+        shape, ss, dtype = ctx.meta
+        gi = _roi_pool_bwd(_pool_grad(grad_out, dtype), boxes, am, shape, ss)
         return gi, None, None, None, None, None, None, None, None
 
 
@@ -188,6 +228,7 @@ def roi_pool_head(input: torch.Tensor, rois: torch.Tensor, roi_inds: torch.Tenso
     """ResnetHead's RoI transform + ``[idx, box]`` pack + roi_pool
     (nets/heads.py:42-48) in one call on device tensors: rois fp32 [R,4] in
     image pixels, roi_inds [R] -> (out [R,C,ph,pw], argmax int32, boxes [R,5]).
+    A float16 / bfloat16 ``input`` stays in its type and ``out`` has it too.
     ``rois_sorted`` promises RoIs grouped by non-decreasing image index (RPN
     proposals, train.py's sample_rois): then the transform runs inside the
     pool kernel.  ``out`` = caller-owned (out, argmax, boxes) buffers
@@ -198,7 +239,7 @@ def roi_pool_head(input: torch.Tensor, rois: torch.Tensor, roi_inds: torch.Tenso
         raise RuntimeError(f"rois must be [R, 4] and roi_inds [R]; got {tuple(rois.shape)}, "
                            f"{tuple(roi_inds.shape)}")
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
-    x = _to_dev(input)
+    x = _to_dev(input) if input.dtype is torch.float32 else _pool_input(input)
     args = (x, _to_dev(rois), _to_dev(roi_inds), int(ph), int(pw), float(img_h), float(img_w),
             float(spatial_scale), bool(rois_sorted))
     if not (torch.is_grad_enabled() and x.requires_grad):  # inference: no autograd node
@@ -221,13 +262,14 @@ def _boxes_to_rois(boxes: Union[torch.Tensor, List[torch.Tensor]]) -> torch.Tens
 def roi_pool_with_argmax(input: torch.Tensor, boxes, output_size, spatial_scale: float = 1.0,
                          rois_sorted=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """roi_pool returning (out, argmax int32) -- the torch.ops.torchvision.roi_pool pair.
+    ``out`` is fp32, or float16 / bfloat16 for an input of that dtype.
     ``rois_sorted``: RoIs grouped by non-decreasing batch index (None = check
     host-resident RoIs, assume unsorted for device RoIs)."""
     if input.dim() != 4:
         raise RuntimeError("input must be [N, C, H, W]")
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
     out_dev = input.device
-    x = _to_dev(input)  # differentiable move, so CPU leaf tensors get their grad
+    x = _pool_input(input)  # differentiable move, so CPU leaf tensors get their grad
     b = _boxes_to_rois(boxes)
     if rois_sorted is None:
         rois_sorted = _sorted_by_image(b)
