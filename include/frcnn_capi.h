@@ -70,6 +70,8 @@ int frcnn_probe_hw_ids(uint32_t* out, int nblocks, int spin, void* stream);
  *                      walks the MT19937 stream) | "chip_only" (no walk behind it) |
  *                      "chip_tight" (zero-margin ranges: exercises the walk behind it);
  *                      the target creators' _draw / _sample entry points
+ *   "rpn_epilogue_strip": "auto" = "64" | "128" (pixels per workgroup strip of the 16-bit
+ *                      frcnn_rpn_head_epilogue_t; the fp32 kernel always takes 64)
  * All paths give bit-identical results.  Not thread-safe against calls in
  * flight on other threads; set it before launching. */
 int frcnn_set_path(const char* op, const char* path);
@@ -484,6 +486,49 @@ int frcnn_losses_fwd(int64_t rows, int C, int P, const float* cls, const float* 
 int frcnn_losses_bwd(int64_t rows, int C, int P, const float* cls, const float* reg, const double* reg_t,
                      const void* labels, int labels_f64, double sigma, const int32_t* stats,
                      const float* g_cls, const float* g_reg, float* dcls, float* dreg, void* stream);
+
+/* ------------------------------------------- predictions in 16-bit types */
+
+/* The ops that read the network's predictions, for float16 / bfloat16
+ * predictions (a network under autocast; DESIGN.md §3 "Predictions in 16-bit
+ * types").  `dtype` (FRCNN_F32 / FRCNN_F16 / FRCNN_BF16) is the element type of
+ * every `void*` prediction argument of the call; all of them share it.
+ * FRCNN_F32 does exactly what the untyped function does (same launches).  For
+ * the 16-bit types each value is widened exactly at the load and the fp32
+ * function's arithmetic runs unchanged, so every fp32 / int32 output is
+ * bit-identical to the untyped function's on the widened inputs; outputs in
+ * the 16-bit type are either copies of input bits or fp32 results rounded once
+ * to nearest even at the store (float16 overflow gives +-inf).  Targets, labels,
+ * RoIs, losses, statistics and workspaces are those of the untyped functions.
+ * Any other dtype code: FRCNN_EINVAL before any HIP call.  A pointer must be
+ * aligned to its element type; wider loads and stores are used where the
+ * addresses allow them.
+ *
+ * frcnn_rpn_head_epilogue_t: cls [N,2K,H,W], reg [N,4K,H,W] of `dtype` ->
+ *   cls_nhwc [N,A,2], reg_nhwc [N,A,4] of `dtype` (the inputs' bit patterns,
+ *   permuted), fg fp32 [N,A], and for the 16-bit types deltas fp32 [N,A,4] =
+ *   reg_nhwc widened, which is what frcnn_propose reads.  With FRCNN_F32 deltas
+ *   is not written and may be NULL (reg_nhwc is the proposal layer's input). */
+int frcnn_rpn_head_epilogue_t(int dtype, const void* cls, const void* reg, int N, int K, int feat_h, int feat_w,
+                              void* cls_nhwc, float* fg, void* reg_nhwc, float* deltas, void* stream);
+/* frcnn_losses_fwd_t / frcnn_losses_bwd_t: cls, reg (and dcls, dreg) of `dtype`.
+ *   loss and stats as frcnn_losses_fwd on the widened inputs; dcls / dreg are
+ *   frcnn_losses_bwd's fp32 values rounded once at the store, never scaled or
+ *   accumulated in 16 bits; every element is stored exactly once (16-byte stores,
+ *   eight elements, where dcls and dreg are 16-byte aligned). */
+int frcnn_losses_fwd_t(int dtype, int64_t rows, int C, int P, const void* cls, const void* reg, const double* reg_t,
+                       const void* labels, int labels_f64, double sigma, float* loss, int32_t* stats,
+                       void* workspace, size_t ws_bytes, void* stream);
+int frcnn_losses_bwd_t(int dtype, int64_t rows, int C, int P, const void* cls, const void* reg, const double* reg_t,
+                       const void* labels, int labels_f64, double sigma, const int32_t* stats, const float* g_cls,
+                       const float* g_reg, void* dcls, void* dreg, void* stream);
+/* frcnn_detect_t: cls [N,R,C] and reg [N,R,4C] of `dtype`; everything else, the
+ *   workspace included, as frcnn_detect. */
+int frcnn_detect_t(int dtype, int N, int R, int C, const float* rois, const int32_t* rcount, const void* cls,
+                   const void* reg, const float* reg_mean, const float* reg_std, float img_h, float img_w,
+                   float score_thresh, double nms_thresh, int max_det, float* det_boxes, int32_t* det_labels,
+                   float* det_scores, int32_t* det_roi, int32_t* det_count, int32_t* det_total, void* workspace,
+                   size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------- preprocessing */
 

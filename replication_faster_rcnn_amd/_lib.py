@@ -55,6 +55,7 @@ SIGNATURES = {
     "frcnn_generate_anchors": (I32, [P, I32, I32, I32, I32, P, P]),
     "frcnn_reg2bbox": (I32, [P, P, I64, P, P]),
     "frcnn_rpn_head_epilogue": (I32, [P, P, I32, I32, I32, I32, P, P, P, P]),
+    "frcnn_rpn_head_epilogue_t": (I32, [I32, P, P, I32, I32, I32, I32, P, P, P, P, P]),
     "frcnn_propose_workspace_size":(SZ, [ctypes.POINTER(ProposeParams)]),
     "frcnn_propose": (I32, [ctypes.POINTER(ProposeParams), P, P, P, P, P, P, P, P, SZ, P]),
     "frcnn_nms_workspace_size": (SZ, [I64]),
@@ -92,12 +93,16 @@ SIGNATURES = {
     "frcnn_detect_workspace_size": (SZ, [I32, I32, I32]),
     "frcnn_detect": (I32, [I32, I32, I32, P, P, P, P, P, P, F32, F32, F32, F64, I32, P, P, P, P, P, P,
                            P, SZ, P]),
+    "frcnn_detect_t": (I32, [I32, I32, I32, I32, P, P, P, P, P, P, F32, F32, F32, F64, I32, P, P, P, P, P, P,
+                             P, SZ, P]),
     "frcnn_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, F64, I32, P, P, P, P, P]),
     "frcnn_eval_ap_workspace_size": (SZ, [I32, I64]),
     "frcnn_eval_ap": (I32, [I32, I64, P, P, P, I32, P, P, P, P, SZ, P]),
     "frcnn_losses_workspace_size": (SZ, [I64, I32]),
     "frcnn_losses_fwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, SZ, P]),
     "frcnn_losses_bwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),
+    "frcnn_losses_fwd_t": (I32, [I32, I64, I32, I32, P, P, P, P, I32, F64, P, P, P, SZ, P]),
+    "frcnn_losses_bwd_t": (I32, [I32, I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),
     "frcnn_preprocess_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
     "frcnn_preprocess": (I32, [I32, P, I64, P, P, I32, I32, I32, I32, P, P, P, P, P, SZ, P]),
     "frcnn_rescale_boxes": (I32, [I32, I32, P, P, I32, I32, P, P]),
@@ -118,6 +123,27 @@ def dtype_code(dtype) -> int:
         return DTYPE_CODES[dtype]
     except KeyError:
         raise RuntimeError(f"RoIPool runs in float32, float16 or bfloat16; got {dtype}") from None
+
+
+def prediction_dtype_code(op: str, tensors) -> int:
+    """The dtype code shared by the prediction inputs of one call of ``op`` (the RPN
+    epilogue, the losses, ``detect``): ``tensors`` is ((name, tensor), ...); all must be
+    device tensors of one dtype out of float32 / float16 / bfloat16.  RuntimeError naming
+    the first offending argument otherwise; attribute reads only."""
+    first = None
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError(f"{op}: {name} must be a device tensor; got {type(t).__name__}")
+        if not t.is_cuda:
+            raise RuntimeError(f"{op}: {name} must be a device tensor; got a {t.dtype} {t.device.type} tensor")
+        if t.dtype not in DTYPE_CODES:
+            raise RuntimeError(f"{op}: {name} must be float32, float16 or bfloat16; got {t.dtype}")
+        if first is None:
+            first = (name, t.dtype)
+        elif t.dtype != first[1]:
+            raise RuntimeError(f"{op}: {name} is {t.dtype} but {first[0]} is {first[1]}; the predictions of one "
+                               "call share one dtype")
+    return DTYPE_CODES[first[1]]
 
 
 _lib = None

@@ -98,6 +98,8 @@ extern "C" int frcnn_set_path(const char* op, const char* path) {
         g_path.roi_split = static_cast<int>(v);
     } else if (is(op, "roi_pool_cg") && (aut || is(path, "4") || is(path, "8") || is(path, "16"))) {
         g_path.roi_cg = aut ? 0 : std::atoi(path);
+    } else if (is(op, "rpn_epilogue_strip") && (aut || is(path, "64") || is(path, "128"))) {
+        g_path.epi_strip = aut ? 0 : std::atoi(path);
     } else {
         set_error("frcnn_set_path: unknown op / path '%s' / '%s'", op, path);
         return FRCNN_EINVAL;

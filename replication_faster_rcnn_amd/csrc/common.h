@@ -36,6 +36,7 @@ struct PathCfg {
     int roi_cg = 0;     // channels per RoIPool workgroup (4 / 8 / 16); 0 = auto
     int sampler = kPathAuto;
     int roi_store = 0;  // RoIPool forward (wave kernel) output stores: 0 temporal (auto), 1 non-temporal
+    int epi_strip = 0;  // 16-bit RPN epilogue: pixels per workgroup strip (64 / 128); 0 = auto (64)
 };
 const PathCfg& path_cfg();
 

@@ -25,7 +25,13 @@
 // Every workspace word a kernel reads was written by an earlier kernel of the
 // same call, and nothing is accumulated with atomics: no state carries over,
 // and results are bit-identical from run to run.
+//
+// float16 / bfloat16 head outputs (frcnn_detect_t; DESIGN.md §3 "Predictions in
+// 16-bit types"): det_softmax_kernel is a template on the element type of cls
+// and det_class_nms_kernel on that of reg, the only two sites that read them;
+// each value is widened at its load and everything behind it is the fp32 code.
 #include "common.h"
+#include "elem16.h"
 #include "nms_iou.h"
 
 namespace frcnn {
@@ -71,7 +77,8 @@ __device__ __forceinline__ int det_valid_rows(const int32_t* rcount, int n, int 
 // fp64-backed exp (the cost), one thread per row for the max and the ordered sum.
 constexpr int kSmRows = 8;
 
-__global__ __launch_bounds__(256) void det_softmax_kernel(const float* __restrict__ cls,
+template <class E>
+__global__ __launch_bounds__(256) void det_softmax_kernel(const typename E::raw* __restrict__ cls,
                                                           const int32_t* __restrict__ rcount, int N, int R,
                                                           int C, float* __restrict__ prob) {
     __shared__ float xs[kSmRows * kDetMaxC];
@@ -80,8 +87,8 @@ __global__ __launch_bounds__(256) void det_softmax_kernel(const float* __restric
     const int row0 = blockIdx.x * kSmRows;
     const int nrow = min(kSmRows, N * R - row0);
     const int ne = nrow * C;
-    const float* x = cls + static_cast<size_t>(row0) * C;
-    for (int i = tid; i < ne; i += 256) xs[i] = x[i];
+    const typename E::raw* x = cls + static_cast<size_t>(row0) * C;
+    for (int i = tid; i < ne; i += 256) xs[i] = E::widen(x[i]);
     __syncthreads();
     if (tid < nrow) {
         const float* v = xs + tid * C;
@@ -113,9 +120,11 @@ struct DetParams {
 };
 
 // blockDim.x = R rounded up to whole waves (<= 1024): thread r owns row r.
+template <class E>
 __global__ __launch_bounds__(1024) void det_class_nms_kernel(DetParams P, const float* __restrict__ rois,
                                                              const int32_t* __restrict__ rcount,
-                                                             const float* __restrict__ reg, NmsThr thr, DetWs w) {
+                                                             const typename E::raw* __restrict__ reg, NmsThr thr,
+                                                             DetWs w) {
     __shared__ uint64_t ckey[kDetMaxR];
     __shared__ float4 cbox[kDetMaxR];
     __shared__ float carea[kDetMaxR];
@@ -166,15 +175,15 @@ __global__ __launch_bounds__(1024) void det_class_nms_kernel(DetParams P, const 
     if (tid < cc) {
         const int r = static_cast<int>(static_cast<uint32_t>(ckey[tid]));  // < k <= R
         const float* a = rois + (static_cast<size_t>(n) * R + r) * 4;
-        const float* d = reg + (static_cast<size_t>(n) * R + r) * 4 * C + 4 * c;
+        const typename E::raw* d = reg + (static_cast<size_t>(n) * R + r) * 4 * C + 4 * c;
         float4 loc;
-        loc.x = d[0] * P.std[0];
+        loc.x = E::widen(d[0]) * P.std[0];
         loc.x = loc.x + P.mean[0];
-        loc.y = d[1] * P.std[1];
+        loc.y = E::widen(d[1]) * P.std[1];
         loc.y = loc.y + P.mean[1];
-        loc.z = d[2] * P.std[2];
+        loc.z = E::widen(d[2]) * P.std[2];
         loc.z = loc.z + P.mean[2];
-        loc.w = d[3] * P.std[3];
+        loc.w = E::widen(d[3]) * P.std[3];
         loc.w = loc.w + P.mean[3];
         float4 b = decode_box(make_float4(a[0], a[1], a[2], a[3]), loc);
         b.x = clamp_nan(b.x, 0.0f, P.img_h);
@@ -314,25 +323,32 @@ extern "C" size_t frcnn_detect_workspace_size(int N, int R, int C) {
     return carve_det(nullptr, N, R, C).bytes;
 }
 
-extern "C" int frcnn_detect(int N, int R, int C, const float* rois, const int32_t* rcount, const float* cls,
-                            const float* reg, const float* reg_mean, const float* reg_std, float img_h,
-                            float img_w, float score_thresh, double nms_thresh, int max_det, float* det_boxes,
-                            int32_t* det_labels, float* det_scores, int32_t* det_roi, int32_t* det_count,
-                            int32_t* det_total, void* workspace, size_t ws_bytes, void* stream) {
-    FRCNN_REQUIRE(N >= 1 && N <= 65535, "frcnn_detect: N=%d must be in [1, 65535]", N);
-    FRCNN_REQUIRE(R >= 1 && R <= kDetMaxR, "frcnn_detect: R=%d must be in [1, %d]", R, kDetMaxR);
-    FRCNN_REQUIRE(C >= 2 && C <= kDetMaxC, "frcnn_detect: C=%d must be in [2, %d]", C, kDetMaxC);
-    FRCNN_REQUIRE(max_det >= 1, "frcnn_detect: max_det=%d must be >= 1", max_det);
-    FRCNN_REQUIRE(static_cast<size_t>(N) * max_det <= (size_t{1} << 30), "frcnn_detect: N*max_det=%zu over 2^30",
+namespace frcnn {
+
+template <class E>
+static int detect_impl(const char* fn, int N, int R, int C, const float* rois, const int32_t* rcount,
+                       const void* cls_v, const void* reg_v, const float* reg_mean, const float* reg_std, float img_h,
+                       float img_w, float score_thresh, double nms_thresh, int max_det, float* det_boxes,
+                       int32_t* det_labels, float* det_scores, int32_t* det_roi, int32_t* det_count,
+                       int32_t* det_total, void* workspace, size_t ws_bytes, void* stream) {
+    const typename E::raw* cls = static_cast<const typename E::raw*>(cls_v);
+    const typename E::raw* reg = static_cast<const typename E::raw*>(reg_v);
+    FRCNN_REQUIRE(N >= 1 && N <= 65535, "%s: N=%d must be in [1, 65535]", fn, N);
+    FRCNN_REQUIRE(R >= 1 && R <= kDetMaxR, "%s: R=%d must be in [1, %d]", fn, R, kDetMaxR);
+    FRCNN_REQUIRE(C >= 2 && C <= kDetMaxC, "%s: C=%d must be in [2, %d]", fn, C, kDetMaxC);
+    FRCNN_REQUIRE(max_det >= 1, "%s: max_det=%d must be >= 1", fn, max_det);
+    FRCNN_REQUIRE(static_cast<size_t>(N) * max_det <= (size_t{1} << 30), "%s: N*max_det=%zu over 2^30", fn,
                   static_cast<size_t>(N) * max_det);
-    FRCNN_REQUIRE(rois && rcount && cls && reg, "frcnn_detect: null input (rois / rcount / cls / reg)");
-    FRCNN_REQUIRE(reg_mean && reg_std, "frcnn_detect: null reg_mean / reg_std");
+    FRCNN_REQUIRE(rois && rcount && cls && reg, "%s: null input (rois / rcount / cls / reg)", fn);
+    FRCNN_REQUIRE(reg_mean && reg_std, "%s: null reg_mean / reg_std", fn);
+    FRCNN_REQUIRE(aligned_to(cls, sizeof(typename E::raw)) && aligned_to(reg, sizeof(typename E::raw)),
+                  "%s: cls / reg not aligned to their element type", fn);
     FRCNN_REQUIRE(det_boxes && det_labels && det_scores && det_roi && det_count && det_total,
-                  "frcnn_detect: null output (det_boxes / det_labels / det_scores / det_roi / det_count / "
-                  "det_total)");
+                  "%s: null output (det_boxes / det_labels / det_scores / det_roi / det_count / "
+                  "det_total)", fn);
     const DetWs w = carve_det(workspace, N, R, C);
     if (!workspace || ws_bytes < w.bytes) {
-        set_error("frcnn_detect: workspace %zu < %zu", workspace ? ws_bytes : size_t{0}, w.bytes);
+        set_error("%s: workspace %zu < %zu", fn, workspace ? ws_bytes : size_t{0}, w.bytes);
         return FRCNN_EWORKSPACE;
     }
     hipStream_t st = as_stream(stream);
@@ -346,13 +362,45 @@ extern "C" int frcnn_detect(int N, int R, int C, const float* rois, const int32_
         P.mean[i] = reg_mean[i];
         P.std[i] = reg_std[i];
     }
-    det_softmax_kernel<<<(N * R + kSmRows - 1) / kSmRows, 256, 0, st>>>(cls, rcount, N, R, C, w.prob);
+    det_softmax_kernel<E><<<(N * R + kSmRows - 1) / kSmRows, 256, 0, st>>>(cls, rcount, N, R, C, w.prob);
     FRCNN_LAUNCH_CHECK("det_softmax_kernel");
     const int threads = (R + 63) / 64 * 64;
-    det_class_nms_kernel<<<dim3(C - 1, N), threads, 0, st>>>(P, rois, rcount, reg, make_thr(nms_thresh), w);
+    det_class_nms_kernel<E><<<dim3(C - 1, N), threads, 0, st>>>(P, rois, rcount, reg, make_thr(nms_thresh), w);
     FRCNN_LAUNCH_CHECK("det_class_nms_kernel");
     det_emit_kernel<<<dim3((max_det + kEmitSlots - 1) / kEmitSlots, N), 256, 0, st>>>(
         R, C, max_det, w, det_boxes, det_labels, det_scores, det_roi, det_count, det_total);
     FRCNN_LAUNCH_CHECK("det_emit_kernel");
     return FRCNN_OK;
+}
+
+}  // namespace frcnn
+
+extern "C" int frcnn_detect(int N, int R, int C, const float* rois, const int32_t* rcount, const float* cls,
+                            const float* reg, const float* reg_mean, const float* reg_std, float img_h,
+                            float img_w, float score_thresh, double nms_thresh, int max_det, float* det_boxes,
+                            int32_t* det_labels, float* det_scores, int32_t* det_roi, int32_t* det_count,
+                            int32_t* det_total, void* workspace, size_t ws_bytes, void* stream) {
+    return detect_impl<ElemF32>("frcnn_detect", N, R, C, rois, rcount, cls, reg, reg_mean, reg_std, img_h, img_w,
+                                score_thresh, nms_thresh, max_det, det_boxes, det_labels, det_scores, det_roi,
+                                det_count, det_total, workspace, ws_bytes, stream);
+}
+
+extern "C" int frcnn_detect_t(int dtype, int N, int R, int C, const float* rois, const int32_t* rcount,
+                              const void* cls, const void* reg, const float* reg_mean, const float* reg_std,
+                              float img_h, float img_w, float score_thresh, double nms_thresh, int max_det,
+                              float* det_boxes, int32_t* det_labels, float* det_scores, int32_t* det_roi,
+                              int32_t* det_count, int32_t* det_total, void* workspace, size_t ws_bytes, void* stream) {
+    FRCNN_REQUIRE(dtype_code_ok(dtype), "frcnn_detect_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16",
+                  dtype);
+    if (dtype == FRCNN_F32)
+        return frcnn_detect(N, R, C, rois, rcount, static_cast<const float*>(cls), static_cast<const float*>(reg),
+                            reg_mean, reg_std, img_h, img_w, score_thresh, nms_thresh, max_det, det_boxes, det_labels,
+                            det_scores, det_roi, det_count, det_total, workspace, ws_bytes, stream);
+    if (dtype == FRCNN_F16)
+        return detect_impl<ElemF16>("frcnn_detect_t", N, R, C, rois, rcount, cls, reg, reg_mean, reg_std, img_h,
+                                    img_w, score_thresh, nms_thresh, max_det, det_boxes, det_labels, det_scores,
+                                    det_roi, det_count, det_total, workspace, ws_bytes, stream);
+    return detect_impl<ElemBF16>("frcnn_detect_t", N, R, C, rois, rcount, cls, reg, reg_mean, reg_std, img_h, img_w,
+                                 score_thresh, nms_thresh, max_det, det_boxes, det_labels, det_scores, det_roi,
+                                 det_count, det_total, workspace, ws_bytes, stream);
 }

@@ -15,7 +15,13 @@
 //
 // No floating-point atomics and no hand-off between workgroups inside a launch:
 // the same inputs give the same bits on every call.
+//
+// float16 / bfloat16 predictions (DESIGN.md §3 "Predictions in 16-bit types"):
+// the kernels are templates on the element type E of cls / reg / dcls / dreg.
+// A 16-bit element is widened at its load, the fp32 / fp64 arithmetic below is
+// the same code, and a gradient is rounded once, at its store.
 #include "common.h"
+#include "elem16.h"
 
 #include <climits>
 #include <cmath>
@@ -99,9 +105,9 @@ __device__ __forceinline__ float sl1_grad(float x, double t64, const LossConsts&
     return diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : diff);  // NaN stays NaN
 }
 
-template <bool F64>
+template <bool F64, class E>
 __global__ __launch_bounds__(kLossThreads) void losses_fwd_kernel(
-    int64_t rows, int C, int P, const float* __restrict__ cls, const float* __restrict__ reg,
+    int64_t rows, int C, int P, const typename E::raw* __restrict__ cls, const typename E::raw* __restrict__ reg,
     const double* __restrict__ reg_t, const void* __restrict__ labels, LossConsts k,
     LossPartial* __restrict__ part) {
     double csum = 0.0, rsum = 0.0;
@@ -113,17 +119,17 @@ __global__ __launch_bounds__(kLossThreads) void losses_fwd_kernel(
         if (l < 0) continue;
         ++nv;
         // -log_softmax(x)[l] = log(sum exp(x - m)) - (x_l - m), the sum in ascending class order
-        const float* x = cls + static_cast<size_t>(r) * C;
-        float m = x[0];
-        for (int c = 1; c < C; ++c) m = x[c] > m ? x[c] : m;
-        float s = exp_cr(x[0] - m);
-        for (int c = 1; c < C; ++c) s = s + exp_cr(x[c] - m);
-        csum += static_cast<double>(log_cr(s) - (x[l] - m));
+        const typename E::raw* x = cls + static_cast<size_t>(r) * C;
+        float m = E::widen(x[0]);
+        for (int c = 1; c < C; ++c) m = E::widen(x[c]) > m ? E::widen(x[c]) : m;
+        float s = exp_cr(E::widen(x[0]) - m);
+        for (int c = 1; c < C; ++c) s = s + exp_cr(E::widen(x[c]) - m);
+        csum += static_cast<double>(log_cr(s) - (E::widen(x[l]) - m));
         if (l > 0) {
             ++np;
-            const float* p = reg + static_cast<size_t>(r) * 4 * P + (P == 1 ? 0 : 4 * l);
+            const typename E::raw* p = reg + static_cast<size_t>(r) * 4 * P + (P == 1 ? 0 : 4 * l);
             const double* t = reg_t + static_cast<size_t>(r) * 4;
-            for (int j = 0; j < 4; ++j) rsum += static_cast<double>(sl1_term(p[j], t[j], k));
+            for (int j = 0; j < 4; ++j) rsum += static_cast<double>(sl1_term(E::widen(p[j]), t[j], k));
         }
     }
     block_sum(csum, rsum, nv, np, ns);
@@ -156,20 +162,23 @@ __global__ __launch_bounds__(kLossThreads) void losses_reduce_kernel(const LossP
 // Few rows get smaller tiles, down to 4 rows, until about two workgroups per CU
 // exist: the exps of a tile are spread over its threads, so the head's 2048
 // rows are one exp per thread instead of C in sequence.
+// 16-bit gradients: the same rule with a multiple of 8 rows (gran = 8), so a tile
+// of dcls (rows * C * 2 B) and of dreg (rows * 4P * 2 B) again starts on a 16-B
+// boundary for every C and P, and a 16-B store holds eight elements.
 __host__ __device__ inline int bwd_stride(int C) { return C | 1; }
-inline int bwd_tile_rows(int64_t rows, int C) {
+inline int bwd_tile_rows(int64_t rows, int C, int gran = 4) {
     int t = kBwdXs / bwd_stride(C);
-    t = (t < kLossThreads ? t : kLossThreads) & ~3;
-    while (t > 4 && (rows + t - 1) / t < 512) t = (t / 2) & ~3;
-    return t < 4 ? 4 : t;
+    t = (t < kLossThreads ? t : kLossThreads) & ~(gran - 1);
+    while (t > gran && (rows + t - 1) / t < 512) t = (t / 2) & ~(gran - 1);
+    return t < gran ? gran : t;
 }
 
-template <bool F64, bool VEC>
+template <bool F64, bool VEC, class E>
 __global__ __launch_bounds__(kLossThreads) void losses_bwd_kernel(
-    int64_t rows, int C, int P, const float* __restrict__ cls, const float* __restrict__ reg,
+    int64_t rows, int C, int P, const typename E::raw* __restrict__ cls, const typename E::raw* __restrict__ reg,
     const double* __restrict__ reg_t, const void* __restrict__ labels, LossConsts k,
     const int32_t* __restrict__ stats, const float* __restrict__ g_cls, const float* __restrict__ g_reg,
-    float* __restrict__ dcls, float* __restrict__ dreg, int T) {
+    typename E::raw* __restrict__ dcls, typename E::raw* __restrict__ dreg, int T) {
     __shared__ float xs[kBwdXs];            // exp(x - max) of the tile's labelled rows
     __shared__ float ssum[kLossThreads];    // their maxima, then their sums
     __shared__ int slab[kLossThreads];      // the tile's labels (-1: nothing to write but zeros)
@@ -192,10 +201,10 @@ __global__ __launch_bounds__(kLossThreads) void losses_bwd_kernel(
         // exp(x - max) and its ascending-order sum for the labelled rows: one thread per
         // logit for the loads and the fp64-backed exps, one per row for the max and the sum
         const int nc = nrow * C;
-        const float* x = cls + static_cast<size_t>(row0) * C;
+        const typename E::raw* x = cls + static_cast<size_t>(row0) * C;
         for (int i = tid; i < nc; i += kLossThreads) {
             const int row = i / C;
-            if (slab[row] >= 0) xs[row * stride + i - row * C] = x[i];
+            if (slab[row] >= 0) xs[row * stride + i - row * C] = E::widen(x[i]);
         }
         __syncthreads();
         if (tid < nrow && slab[tid] >= 0) {
@@ -236,13 +245,44 @@ __global__ __launch_bounds__(kLossThreads) void losses_bwd_kernel(
         const int l = slab[row];
         if (l <= 0 || !do_reg || (P != 1 && (col >> 2) != l)) return 0.0f;
         const size_t r = static_cast<size_t>(row0 + row);
-        return sl1_grad(reg[r * W + col], reg_t[r * 4 + (col & 3)], k) * scale_r;
+        return sl1_grad(E::widen(reg[r * W + col]), reg_t[r * 4 + (col & 3)], k) * scale_r;
     };
 
-    float* oc = dcls + static_cast<size_t>(row0) * C;
-    float* orr = dreg + static_cast<size_t>(row0) * W;
+    typename E::raw* oc = dcls + static_cast<size_t>(row0) * C;
+    typename E::raw* orr = dreg + static_cast<size_t>(row0) * W;
     const int nc = nrow * C, nr = nrow * W;
-    if (VEC) {  // both tiles start 16-B aligned (T % 4 == 0); nr % 4 == 0, nc's tail is scalar
+    if constexpr (sizeof(typename E::raw) == 2) {
+        // the one rounding of each gradient; two elements per 32-bit word, low half first
+        auto pack2 = [&](float a, float b) -> uint32_t {
+            return static_cast<uint32_t>(E::narrow(a)) | (static_cast<uint32_t>(E::narrow(b)) << 16);
+        };
+        if (VEC) {  // both tiles start 16-B aligned (T % 8 == 0): eight elements per store, the tails single
+            for (int q = tid; q < nc / 8; q += kLossThreads) {
+                const int i = 8 * q;
+                reinterpret_cast<uint4*>(oc)[q] =
+                    make_uint4(pack2(dcls_at(i), dcls_at(i + 1)), pack2(dcls_at(i + 2), dcls_at(i + 3)),
+                               pack2(dcls_at(i + 4), dcls_at(i + 5)), pack2(dcls_at(i + 6), dcls_at(i + 7)));
+            }
+            for (int i = (nc & ~7) + tid; i < nc; i += kLossThreads) oc[i] = E::narrow(dcls_at(i));
+            for (int q = tid; q < nr / 8; q += kLossThreads) {  // two groups of four columns, each within a row
+                const int ra = (2 * q) / P, ca = 4 * (2 * q - ra * P);
+                const int rb = (2 * q + 1) / P, cb = 4 * (2 * q + 1 - rb * P);
+                reinterpret_cast<uint4*>(orr)[q] =
+                    make_uint4(pack2(dreg_at(ra, ca), dreg_at(ra, ca + 1)), pack2(dreg_at(ra, ca + 2), dreg_at(ra, ca + 3)),
+                               pack2(dreg_at(rb, cb), dreg_at(rb, cb + 1)), pack2(dreg_at(rb, cb + 2), dreg_at(rb, cb + 3)));
+            }
+            for (int i = (nr & ~7) + tid; i < nr; i += kLossThreads) {
+                const int row = i / W;
+                orr[i] = E::narrow(dreg_at(row, i - row * W));
+            }
+        } else {
+            for (int i = tid; i < nc; i += kLossThreads) oc[i] = E::narrow(dcls_at(i));
+            for (int i = tid; i < nr; i += kLossThreads) {
+                const int row = i / W;
+                orr[i] = E::narrow(dreg_at(row, i - row * W));
+            }
+        }
+    } else if (VEC) {  // both tiles start 16-B aligned (T % 4 == 0); nr % 4 == 0, nc's tail is scalar
         for (int q = tid; q < nc / 4; q += kLossThreads)
             reinterpret_cast<float4*>(oc)[q] =
                 make_float4(dcls_at(4 * q), dcls_at(4 * q + 1), dcls_at(4 * q + 2), dcls_at(4 * q + 3));
@@ -280,6 +320,73 @@ int check_stage(const char* fn, int64_t rows, int C, int P, double sigma, LossCo
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+template <class E>
+int losses_fwd_impl(const char* fn, int64_t rows, int C, int P, const void* cls_v, const void* reg_v,
+                    const double* reg_t, const void* labels, int labels_f64, double sigma, float* loss,
+                    int32_t* stats, void* workspace, size_t ws_bytes, void* stream) {
+    using R = typename E::raw;
+    const R* cls = static_cast<const R*>(cls_v);
+    const R* reg = static_cast<const R*>(reg_v);
+    LossConsts k;
+    if (int rc = check_stage(fn, rows, C, P, sigma, &k)) return rc;
+    FRCNN_REQUIRE(loss && stats, "%s: null output (loss / stats)", fn);
+    FRCNN_REQUIRE(rows == 0 || (cls && reg && reg_t && labels), "%s: null input (cls / reg / reg_t / labels)", fn);
+    FRCNN_REQUIRE(aligned_to(cls, sizeof(R)) && aligned_to(reg, sizeof(R)),
+                  "%s: cls / reg not aligned to their element type", fn);
+    const size_t need = frcnn_losses_workspace_size(rows, C);
+    if (need > 0 && (!workspace || ws_bytes < need)) {
+        set_error("%s: workspace of %zu B < %zu B", fn, workspace ? ws_bytes : size_t{0}, need);
+        return FRCNN_EWORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    LossPartial* part = static_cast<LossPartial*>(workspace);
+    const int nb = fwd_blocks(rows);
+    if (nb > 0) {
+        if (labels_f64)
+            losses_fwd_kernel<true, E><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, part);
+        else
+            losses_fwd_kernel<false, E><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, part);
+        FRCNN_LAUNCH_CHECK("losses_fwd_kernel");
+    }
+    losses_reduce_kernel<<<1, kLossThreads, 0, st>>>(part, nb, loss, stats);
+    FRCNN_LAUNCH_CHECK("losses_reduce_kernel");
+    return FRCNN_OK;
+}
+
+template <class E>
+int losses_bwd_impl(const char* fn, int64_t rows, int C, int P, const void* cls_v, const void* reg_v,
+                    const double* reg_t, const void* labels, int labels_f64, double sigma, const int32_t* stats,
+                    const float* g_cls, const float* g_reg, void* dcls_v, void* dreg_v, void* stream) {
+    using R = typename E::raw;
+    const R* cls = static_cast<const R*>(cls_v);
+    const R* reg = static_cast<const R*>(reg_v);
+    R* dcls = static_cast<R*>(dcls_v);
+    R* dreg = static_cast<R*>(dreg_v);
+    LossConsts k;
+    if (int rc = check_stage(fn, rows, C, P, sigma, &k)) return rc;
+    if (rows == 0) return FRCNN_OK;  // no output elements
+    FRCNN_REQUIRE(cls && reg && reg_t && labels && stats, "%s: null input (cls / reg / reg_t / labels / stats)", fn);
+    FRCNN_REQUIRE(dcls && dreg, "%s: null output (dcls / dreg)", fn);
+    FRCNN_REQUIRE(aligned_to(cls, sizeof(R)) && aligned_to(reg, sizeof(R)) && aligned_to(dcls, sizeof(R)) &&
+                      aligned_to(dreg, sizeof(R)),
+                  "%s: cls / reg / dcls / dreg not aligned to their element type", fn);
+    hipStream_t st = as_stream(stream);
+    const int T = bwd_tile_rows(rows, C, sizeof(R) == 2 ? 8 : 4);
+    const int nb = static_cast<int>((rows + T - 1) / T);
+    const bool vec = aligned16(dcls) && aligned16(dreg);
+#define FRCNN_LOSSES_BWD(F64, VEC)                                                                               \
+    losses_bwd_kernel<F64, VEC, E><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, stats, \
+                                                                g_cls, g_reg, dcls, dreg, T)
+    if (labels_f64) {
+        if (vec) FRCNN_LOSSES_BWD(true, true); else FRCNN_LOSSES_BWD(true, false);
+    } else {
+        if (vec) FRCNN_LOSSES_BWD(false, true); else FRCNN_LOSSES_BWD(false, false);
+    }
+#undef FRCNN_LOSSES_BWD
+    FRCNN_LAUNCH_CHECK("losses_bwd_kernel");
+    return FRCNN_OK;
+}
+
 }  // namespace
 }  // namespace frcnn
 
@@ -293,53 +400,45 @@ extern "C" size_t frcnn_losses_workspace_size(int64_t rows, int C) {
 extern "C" int frcnn_losses_fwd(int64_t rows, int C, int P, const float* cls, const float* reg, const double* reg_t,
                                 const void* labels, int labels_f64, double sigma, float* loss, int32_t* stats,
                                 void* workspace, size_t ws_bytes, void* stream) {
-    LossConsts k;
-    if (int rc = check_stage("frcnn_losses_fwd", rows, C, P, sigma, &k)) return rc;
-    FRCNN_REQUIRE(loss && stats, "frcnn_losses_fwd: null output (loss / stats)");
-    FRCNN_REQUIRE(rows == 0 || (cls && reg && reg_t && labels),
-                  "frcnn_losses_fwd: null input (cls / reg / reg_t / labels)");
-    const size_t need = frcnn_losses_workspace_size(rows, C);
-    if (need > 0 && (!workspace || ws_bytes < need)) {
-        set_error("frcnn_losses_fwd: workspace of %zu B < %zu B", workspace ? ws_bytes : size_t{0}, need);
-        return FRCNN_EWORKSPACE;
-    }
-    hipStream_t st = as_stream(stream);
-    LossPartial* part = static_cast<LossPartial*>(workspace);
-    const int nb = fwd_blocks(rows);
-    if (nb > 0) {
-        if (labels_f64)
-            losses_fwd_kernel<true><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, part);
-        else
-            losses_fwd_kernel<false><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, part);
-        FRCNN_LAUNCH_CHECK("losses_fwd_kernel");
-    }
-    losses_reduce_kernel<<<1, kLossThreads, 0, st>>>(part, nb, loss, stats);
-    FRCNN_LAUNCH_CHECK("losses_reduce_kernel");
-    return FRCNN_OK;
+    return losses_fwd_impl<ElemF32>("frcnn_losses_fwd", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma, loss,
+                                    stats, workspace, ws_bytes, stream);
 }
 
 extern "C" int frcnn_losses_bwd(int64_t rows, int C, int P, const float* cls, const float* reg, const double* reg_t,
                                 const void* labels, int labels_f64, double sigma, const int32_t* stats,
                                 const float* g_cls, const float* g_reg, float* dcls, float* dreg, void* stream) {
-    LossConsts k;
-    if (int rc = check_stage("frcnn_losses_bwd", rows, C, P, sigma, &k)) return rc;
-    if (rows == 0) return FRCNN_OK;  // no output elements
-    FRCNN_REQUIRE(cls && reg && reg_t && labels && stats,
-                  "frcnn_losses_bwd: null input (cls / reg / reg_t / labels / stats)");
-    FRCNN_REQUIRE(dcls && dreg, "frcnn_losses_bwd: null output (dcls / dreg)");
-    hipStream_t st = as_stream(stream);
-    const int T = bwd_tile_rows(rows, C);
-    const int nb = static_cast<int>((rows + T - 1) / T);
-    const bool vec = aligned16(dcls) && aligned16(dreg);
-#define FRCNN_LOSSES_BWD(F64, VEC)                                                                            \
-    losses_bwd_kernel<F64, VEC><<<nb, kLossThreads, 0, st>>>(rows, C, P, cls, reg, reg_t, labels, k, stats, \
-                                                             g_cls, g_reg, dcls, dreg, T)
-    if (labels_f64) {
-        if (vec) FRCNN_LOSSES_BWD(true, true); else FRCNN_LOSSES_BWD(true, false);
-    } else {
-        if (vec) FRCNN_LOSSES_BWD(false, true); else FRCNN_LOSSES_BWD(false, false);
-    }
-#undef FRCNN_LOSSES_BWD
-    FRCNN_LAUNCH_CHECK("losses_bwd_kernel");
-    return FRCNN_OK;
+    return losses_bwd_impl<ElemF32>("frcnn_losses_bwd", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma, stats,
+                                    g_cls, g_reg, dcls, dreg, stream);
+}
+
+extern "C" int frcnn_losses_fwd_t(int dtype, int64_t rows, int C, int P, const void* cls, const void* reg,
+                                  const double* reg_t, const void* labels, int labels_f64, double sigma, float* loss,
+                                  int32_t* stats, void* workspace, size_t ws_bytes, void* stream) {
+    FRCNN_REQUIRE(dtype_code_ok(dtype), "frcnn_losses_fwd_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16",
+                  dtype);
+    if (dtype == FRCNN_F32)
+        return frcnn_losses_fwd(rows, C, P, static_cast<const float*>(cls), static_cast<const float*>(reg), reg_t,
+                                labels, labels_f64, sigma, loss, stats, workspace, ws_bytes, stream);
+    if (dtype == FRCNN_F16)
+        return losses_fwd_impl<ElemF16>("frcnn_losses_fwd_t", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma,
+                                        loss, stats, workspace, ws_bytes, stream);
+    return losses_fwd_impl<ElemBF16>("frcnn_losses_fwd_t", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma,
+                                     loss, stats, workspace, ws_bytes, stream);
+}
+
+extern "C" int frcnn_losses_bwd_t(int dtype, int64_t rows, int C, int P, const void* cls, const void* reg,
+                                  const double* reg_t, const void* labels, int labels_f64, double sigma,
+                                  const int32_t* stats, const float* g_cls, const float* g_reg, void* dcls, void* dreg,
+                                  void* stream) {
+    FRCNN_REQUIRE(dtype_code_ok(dtype), "frcnn_losses_bwd_t: dtype code %d is not FRCNN_F32, FRCNN_F16 or FRCNN_BF16",
+                  dtype);
+    if (dtype == FRCNN_F32)
+        return frcnn_losses_bwd(rows, C, P, static_cast<const float*>(cls), static_cast<const float*>(reg), reg_t,
+                                labels, labels_f64, sigma, stats, g_cls, g_reg, static_cast<float*>(dcls),
+                                static_cast<float*>(dreg), stream);
+    if (dtype == FRCNN_F16)
+        return losses_bwd_impl<ElemF16>("frcnn_losses_bwd_t", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma,
+                                        stats, g_cls, g_reg, dcls, dreg, stream);
+    return losses_bwd_impl<ElemBF16>("frcnn_losses_bwd_t", rows, C, P, cls, reg, reg_t, labels, labels_f64, sigma,
+                                     stats, g_cls, g_reg, dcls, dreg, stream);
 }

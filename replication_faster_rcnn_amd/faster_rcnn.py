@@ -44,7 +44,8 @@ class FasterRCNN(nn.Module):
         ``rpn.rois_count`` are ignored by ``ops.detect``), so the whole stage
         is fixed-shape; the only host read is the final counts.  The padded
         device tensors stay in ``self.last_detections``, the head outputs as
-        ``(cls [N,R,C], reg [N,R,4C])`` in ``self.last_head_outputs``."""
+        ``(cls [N,R,C], reg [N,R,4C])`` in ``self.last_head_outputs``, in
+        their own dtype (fp32, or float16 / bfloat16 under autocast)."""
         features = self.backbone(x)
         self.rpn(features, width, height)
         rois_p, cnt = self.rpn.rois_padded, self.rpn.rois_count
@@ -52,8 +53,10 @@ class FasterRCNN(nn.Module):
         roi_inds = torch.arange(N, dtype=torch.float32, device=rois_p.device).repeat_interleave(R)
         cls, reg = self.head(features, rois_p.view(N * R, 4), roi_inds, height, width, rois_sorted=True)
         dev = _lib.device()
-        cls = cls.permute(0, 2, 1).to(dev, torch.float32).contiguous()
-        reg = reg.to(dev, torch.float32).contiguous()
+        # fp32, or the float16 / bfloat16 a head under autocast returns: ops.detect reads either as it is
+        keep = (torch.float32, torch.float16, torch.bfloat16)
+        cls = cls.permute(0, 2, 1).to(dev, cls.dtype if cls.dtype in keep else torch.float32).contiguous()
+        reg = reg.to(dev, reg.dtype if reg.dtype in keep else torch.float32).contiguous()
         self.last_head_outputs = (cls, reg)
         det = ops.detect(rois_p, cnt, cls, reg, img_h=height, img_w=width, score_thresh=score_thresh,
                          nms_thresh=nms_thresh, max_det=max_det)

@@ -35,11 +35,16 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   the gradient have the input's dtype as torchvision's do, and the kernels
   read and write the 16-bit values directly (DESIGN.md §3 "RoIPool in 16-bit
   types").  ``boxes`` / ``rois`` / ``roi_inds`` stay fp32, ``argmax`` int32.
+  The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
+  (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
 * The hot-path ops on device tensors (``propose``, ``roi_transform``,
   ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
+  The predictions ``cls`` / ``reg`` of ``detect``, ``rpn_losses`` and
+  ``head_losses`` may be float16 or bfloat16 instead of fp32, both in the same
+  dtype (DESIGN.md §3 "Predictions in 16-bit types").
 
 Errors follow torchvision's ``TORCH_CHECK`` -> ``RuntimeError`` convention.
 """
@@ -371,16 +376,19 @@ def detect(rois: torch.Tensor, rcount: torch.Tensor, cls: torch.Tensor, reg: tor
     and per-class NMS for the whole batch.
 
     rois fp32 [N, R, 4] + rcount int32 [N] (``RPN.rois_padded`` / ``rois_count``
-    as they are), cls fp32 [N, R, C] logits (``ResnetHead`` returns the
-    ``[N, C, R]`` view: pass ``cls.permute(0, 2, 1).contiguous()``), reg fp32
-    [N, R, 4C].  Returns padded (det_boxes [N, max_det, 4], det_labels int32
+    as they are), cls [N, R, C] logits (``ResnetHead`` returns the
+    ``[N, C, R]`` view: pass ``cls.permute(0, 2, 1).contiguous()``), reg
+    [N, R, 4C]; cls and reg are both fp32, both float16 or both bfloat16 (a head
+    under autocast; widened exactly inside the kernels, every output is the fp32
+    op's on the widened inputs).  Returns padded (det_boxes [N, max_det, 4], det_labels int32
     [N, max_det], det_scores [N, max_det], det_roi int32 [N, max_det], det_count
     int32 [N], det_total int32 [N]) -- no host synchronisation.  ``max_det``
     defaults to R*(C-1), which never truncates.
     """
     lib = _lib.load()
+    code = _lib.prediction_dtype_code("detect", (("cls", cls), ("reg", reg)))
     for name, t, dt in (("rois", rois, torch.float32), ("rcount", rcount, torch.int32),
-                        ("cls", cls, torch.float32), ("reg", reg, torch.float32)):
+                        ("cls", cls, cls.dtype), ("reg", reg, cls.dtype)):
         if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
             raise RuntimeError(f"detect: {name} must be a contiguous {dt} device tensor")
     if cls.dim() != 3:
@@ -420,11 +428,11 @@ def detect(rois: torch.Tensor, rcount: torch.Tensor, cls: torch.Tensor, reg: tor
     if need and ws.numel() < need:
         raise RuntimeError(f"detect: workspace of {ws.numel()} B < {need} B")
     boxes, labels, scores, roi, count, total = out
-    _lib.check(lib.frcnn_detect(N, R, C, _lib.ptr(rois), _lib.ptr(rcount), _lib.ptr(cls), _lib.ptr(reg),
-                                mean, std, float(img_h), float(img_w), float(score_thresh),
-                                float(nms_thresh), max_det, _lib.ptr(boxes), _lib.ptr(labels),
-                                _lib.ptr(scores), _lib.ptr(roi), _lib.ptr(count), _lib.ptr(total),
-                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "detect")
+    _lib.check(lib.frcnn_detect_t(code, N, R, C, _lib.ptr(rois), _lib.ptr(rcount), _lib.ptr(cls), _lib.ptr(reg),
+                                  mean, std, float(img_h), float(img_w), float(score_thresh),
+                                  float(nms_thresh), max_det, _lib.ptr(boxes), _lib.ptr(labels),
+                                  _lib.ptr(scores), _lib.ptr(roi), _lib.ptr(count), _lib.ptr(total),
+                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "detect")
     return boxes, labels, scores, roi, count, total
 
 
@@ -536,8 +544,9 @@ def eval_ap(state, n_records: int = None, *, use_07_metric: bool = False, return
 # ------------------------------------------------------------- RPN epilogue
 class _RPNHeadEpilogueFunction(torch.autograd.Function):
     """nets/rpn.py:117-124 as one launch.  The backward of the two permutes is
-    the inverse permute (plain tensor ops); the fg scores feed only the
-    (non-differentiable) proposal layer, as in the reference."""
+    the inverse permute (plain tensor ops, in the gradients' own dtype); the fg
+    scores feed only the (non-differentiable) proposal layer, as in the
+    reference.  float16 / bfloat16 inputs give a fourth output, the fp32 deltas."""
 
     @staticmethod
     def forward(ctx, cls, reg, K):
@@ -547,18 +556,29 @@ class _RPNHeadEpilogueFunction(torch.autograd.Function):
             raise RuntimeError(f"rpn_head_epilogue: cls {tuple(cls.shape)} / reg {tuple(reg.shape)} "
                                f"do not match K={K}")
         A = H * W * K
-        cls_nhwc = torch.empty((N, A, 2), dtype=torch.float32, device=cls.device)
+        dt = cls.dtype  # fp32, or the 16-bit type both conv outputs share (rpn_head_epilogue's rule)
+        cls_nhwc = torch.empty((N, A, 2), dtype=dt, device=cls.device)
         fg = torch.empty((N, A), dtype=torch.float32, device=cls.device)
-        reg_nhwc = torch.empty((N, A, 4), dtype=torch.float32, device=cls.device)
-        _lib.check(lib.frcnn_rpn_head_epilogue(_lib.ptr(cls), _lib.ptr(reg), N, K, H, W,
-                                               _lib.ptr(cls_nhwc), _lib.ptr(fg), _lib.ptr(reg_nhwc),
-                                               _lib.stream_ptr()), "rpn_head_epilogue")
+        reg_nhwc = torch.empty((N, A, 4), dtype=dt, device=cls.device)
+        if dt == torch.float32:
+            _lib.check(lib.frcnn_rpn_head_epilogue(_lib.ptr(cls), _lib.ptr(reg), N, K, H, W,
+                                                   _lib.ptr(cls_nhwc), _lib.ptr(fg), _lib.ptr(reg_nhwc),
+                                                   _lib.stream_ptr()), "rpn_head_epilogue")
+            deltas = None  # reg_nhwc is the proposal layer's input (rpn_head_epilogue_with_deltas)
+        else:
+            deltas = torch.empty((N, A, 4), dtype=torch.float32, device=cls.device)
+            _lib.check(lib.frcnn_rpn_head_epilogue_t(_lib.DTYPE_CODES[dt], _lib.ptr(cls), _lib.ptr(reg), N, K, H, W,
+                                                     _lib.ptr(cls_nhwc), _lib.ptr(fg), _lib.ptr(reg_nhwc),
+                                                     _lib.ptr(deltas), _lib.stream_ptr()), "rpn_head_epilogue")
         ctx.meta = (N, K, H, W)
-        ctx.mark_non_differentiable(fg)
-        return cls_nhwc, fg, reg_nhwc
+        if deltas is None:
+            ctx.mark_non_differentiable(fg)
+            return cls_nhwc, fg, reg_nhwc
+        ctx.mark_non_differentiable(fg, deltas)
+        return cls_nhwc, fg, reg_nhwc, deltas
 
     @staticmethod
-    def backward(ctx, g_cls, _g_fg, g_reg):
+    def backward(ctx, g_cls, _g_fg, g_reg, _g_deltas=None):
         N, K, H, W = ctx.meta
         gc = gr = None
         if g_cls is not None:
@@ -568,14 +588,41 @@ class _RPNHeadEpilogueFunction(torch.autograd.Function):
         return gc, gr, None
 
 
-def rpn_head_epilogue(cls: torch.Tensor, reg: torch.Tensor, K: int):
-    """nets/rpn.py:117-124: conv outputs cls [N,2K,H,W], reg [N,4K,H,W] (device,
-    fp32) -> (cls_nhwc [N,A,2], fg [N,A], reg_nhwc [N,A,4]), A = H*W*K.
-    ``cls_nhwc.permute(0, 2, 1)`` is the reference's returned ``cls``; ``fg`` is
-    its ``cls_fg_softmax``; ``reg_nhwc`` its ``reg``."""
-    if cls.dim() != 4 or reg.dim() != 4:
+def _epilogue_inputs(cls, reg):
+    if not isinstance(cls, torch.Tensor) or not isinstance(reg, torch.Tensor) or cls.dim() != 4 or reg.dim() != 4:
         raise RuntimeError("rpn_head_epilogue: cls and reg must be NCHW")
-    return _RPNHeadEpilogueFunction.apply(cls.float().contiguous(), reg.float().contiguous(), int(K))
+    if cls.dtype in _POOL_HALF or reg.dtype in _POOL_HALF:
+        if reg.dtype != cls.dtype:
+            raise RuntimeError(f"rpn_head_epilogue: reg is {reg.dtype} but cls is {cls.dtype}; a float16 or "
+                               "bfloat16 conv output needs its partner in the same dtype")
+        return _to_dev(cls, cls.dtype), _to_dev(reg, reg.dtype)  # moved / made contiguous if needed, never widened
+    return cls.float().contiguous(), reg.float().contiguous()
+
+
+def rpn_head_epilogue_with_deltas(cls: torch.Tensor, reg: torch.Tensor, K: int):
+    """``rpn_head_epilogue`` plus the proposal layer's deltas: (cls_nhwc, fg,
+    reg_nhwc, deltas).  ``deltas`` is fp32 [N,A,4] and non-differentiable: for
+    fp32 inputs ``reg_nhwc`` itself (detached), for float16 / bfloat16 inputs the
+    widened ``reg_nhwc``, written by the same launch -- feed it to ``propose``."""
+    c, r = _epilogue_inputs(cls, reg)
+    out = _RPNHeadEpilogueFunction.apply(c, r, int(K))
+    return out if len(out) == 4 else (*out, out[2].detach())
+
+
+def rpn_head_epilogue(cls: torch.Tensor, reg: torch.Tensor, K: int):
+    """nets/rpn.py:117-124: conv outputs cls [N,2K,H,W], reg [N,4K,H,W] (device)
+    -> (cls_nhwc [N,A,2], fg [N,A], reg_nhwc [N,A,4]), A = H*W*K.
+    ``cls_nhwc.permute(0, 2, 1)`` is the reference's returned ``cls``; ``fg`` is
+    its ``cls_fg_softmax``; ``reg_nhwc`` its ``reg``.
+
+    float16 / bfloat16 conv outputs (a network under autocast; both of the same
+    dtype, RuntimeError otherwise) keep their type: ``cls_nhwc`` and ``reg_nhwc``
+    then have the inputs' dtype and exactly their bit patterns (they were fp32
+    before this op read 16-bit inputs itself), the gradients arrive in that dtype,
+    and ``fg`` stays fp32, bit-equal to the fp32 op's on the widened inputs
+    (DESIGN.md §3 "Predictions in 16-bit types").  Every other dtype is
+    converted to fp32 as before."""
+    return rpn_head_epilogue_with_deltas(cls, reg, K)[:3]
 
 
 def roi_transform(rois: torch.Tensor, roi_inds: torch.Tensor, img_h, img_w, feat_h: int,
@@ -610,6 +657,7 @@ class _LossesFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cls, reg, reg_t, labels, sigma, P, permuted):
         lib = _lib.load()
+        code = _lib.DTYPE_CODES[cls.dtype]  # cls and reg share it (_losses)
         N, L, C = cls.permute(0, 2, 1).shape if permuted else cls.shape
         rows = N * L
         dev = cls.device
@@ -620,11 +668,11 @@ class _LossesFunction(torch.autograd.Function):
             need = _losses_ws[(rows, C)] = int(lib.frcnn_losses_workspace_size(rows, C))
         ws = _lib.cached_workspace("losses", need, dev)
         f64 = int(labels.dtype == torch.float64)
-        _lib.check(lib.frcnn_losses_fwd(rows, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
-                                        _lib.ptr(labels), f64, sigma, _lib.ptr(loss), _lib.ptr(stats),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "losses forward")
+        _lib.check(lib.frcnn_losses_fwd_t(code, rows, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
+                                          _lib.ptr(labels), f64, sigma, _lib.ptr(loss), _lib.ptr(stats),
+                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "losses forward")
         ctx.save_for_backward(cls, reg, reg_t, labels, stats)
-        ctx.meta = (N, L, C, P, f64, sigma, permuted)
+        ctx.meta = (N, L, C, P, f64, sigma, permuted, code)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(stats)
         return loss[0], loss[1], stats
@@ -634,16 +682,17 @@ class _LossesFunction(torch.autograd.Function):
     def backward(ctx, g_cls, g_reg, _g_stats):
         lib = _lib.load()
         cls, reg, reg_t, labels, stats = ctx.saved_tensors
-        N, L, C, P, f64, sigma, permuted = ctx.meta
+        N, L, C, P, f64, sigma, permuted, code = ctx.meta
         for name, g in (("cls_loss", g_cls), ("reg_loss", g_reg)):
             if g is not None and (g.dtype != torch.float32 or not g.is_cuda or g.numel() != 1):
                 raise RuntimeError(f"losses backward: the gradient of {name} must be one torch.float32 on the "
                                    f"device; got {g.dtype} on {g.device.type} with {g.numel()} elements")
-        dcls = torch.empty((N, L, C), dtype=torch.float32, device=cls.device)
-        dreg = torch.empty((N, L, 4 * P), dtype=torch.float32, device=cls.device)
-        _lib.check(lib.frcnn_losses_bwd(N * L, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
-                                        _lib.ptr(labels), f64, sigma, _lib.ptr(stats), _lib.ptr(g_cls),
-                                        _lib.ptr(g_reg), _lib.ptr(dcls), _lib.ptr(dreg), _lib.stream_ptr()),
+        # gradients in the predictions' dtype: the kernel rounds each fp32 value once, at its store
+        dcls = torch.empty((N, L, C), dtype=cls.dtype, device=cls.device)
+        dreg = torch.empty((N, L, 4 * P), dtype=cls.dtype, device=cls.device)
+        _lib.check(lib.frcnn_losses_bwd_t(code, N * L, C, P, _lib.ptr(cls), _lib.ptr(reg), _lib.ptr(reg_t),
+                                          _lib.ptr(labels), f64, sigma, _lib.ptr(stats), _lib.ptr(g_cls),
+                                          _lib.ptr(g_reg), _lib.ptr(dcls), _lib.ptr(dreg), _lib.stream_ptr()),
                    "losses backward")
         return (dcls.permute(0, 2, 1) if permuted else dcls), dreg, None, None, None, None, None
 
@@ -664,9 +713,11 @@ def _losses(op, cls, reg, reg_targets, labels, sigma, head, return_stats):
     permuted = not cls.is_contiguous() and cls.permute(0, 2, 1).is_contiguous()
     rows_first = cls.permute(0, 2, 1) if permuted else cls
     C = rows_first.shape[2]
-    _require(op, "cls", rows_first, torch.float32, (N, L, C))
+    # fp32, or float16 / bfloat16 predictions of a network under autocast: cls and reg in one dtype
+    dt = cls.dtype if cls.dtype in _POOL_HALF else torch.float32
+    _require(op, "cls", rows_first, dt, (N, L, C))
     P = C if head else 1
-    _require(op, "reg", reg, torch.float32, (N, L, 4 * P))
+    _require(op, "reg", reg, dt, (N, L, 4 * P))
     _require(op, "reg_targets", reg_targets, torch.float64, (N, L, 4))
     if not 2 <= C <= 128:
         raise RuntimeError(f"{op}: cls has C={C} classes; must be in [2, 128]")
@@ -685,7 +736,10 @@ def rpn_losses(cls: torch.Tensor, reg: torch.Tensor, reg_targets: torch.Tensor, 
     with label > 0, divided by max(#positives, 1).
 
     cls fp32 [N, A, 2] -- or the [N, 2, A] view of one that ``RPN.forward``
-    returns, accepted as it is --, reg fp32 [N, A, 4], reg_targets fp64
+    returns, accepted as it is --, reg fp32 [N, A, 4] (or both float16 / both
+    bfloat16, the predictions of a network under autocast: widened exactly in
+    the kernels, losses bit-equal to the fp32 op's on the widened inputs, the
+    gradients in that dtype, each the fp32 gradient rounded once), reg_targets fp64
     [N, A, 4] and labels int32 (or fp64) [N, A] exactly as
     ``targets.anchor_targets`` returns them.  Returns (cls_loss, reg_loss), 0-dim
     fp32 device tensors.

@@ -92,7 +92,9 @@ class RPN(nn.Module):
         # nets/rpn.py:117-124: permute/contiguous/softmax/slice in ONE launch
         # (ops.rpn_head_epilogue); results return to x's device like the reference's
         dev = _lib.device()
-        cls_nhwc, cls_fg_softmax, reg = ops.rpn_head_epilogue(
+        # (under autocast the convs return float16 / bfloat16: cls and reg keep that type, the
+        # fg scores and the proposal layer's deltas come out of the same launch as fp32)
+        cls_nhwc, cls_fg_softmax, reg, deltas = ops.rpn_head_epilogue_with_deltas(
             self.cls(x).to(dev), self.reg(x).to(dev), self.K)
         cls = cls_nhwc.to(x.device).permute(0, 2, 1)
 
@@ -101,7 +103,7 @@ class RPN(nn.Module):
                                                          anchor_scales=self._scales)
         pl = self.proposal_layer
         rois_p, _, cnt = ops.propose(
-            cls_fg_softmax, reg.detach(), img_w=img_width, img_h=img_height,
+            cls_fg_softmax, deltas, img_w=img_width, img_h=img_height,
             pre_nms=pl.pre_nms, post_nms=pl.post_nms, nms_thresh=pl.nms_threshold,
             min_size=pl.min_size, anchor_base=self._base_dev, feat_h=conv_h, feat_w=conv_w,
             feat_stride=self.feat_stride)

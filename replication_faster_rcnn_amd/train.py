@@ -47,14 +47,22 @@ class Trainer:
     gathers (a host synchronisation each) and no ``reg_ind`` gather, which the
     head's kernel does itself.  ``last["reg_output"]`` then holds the ungathered
     ``[N, S, 4C]`` head output instead of the gathered ``[N, S, 4]``.  The
-    default keeps the dense PyTorch losses."""
+    default keeps the dense PyTorch losses.
 
-    def __init__(self, rpn, head, n_sample=(256, 128), optimizer=None, fused_losses=False):
+    Under ``torch.autocast("cuda", dtype=torch.float16 / torch.bfloat16)`` the
+    fused losses read the 16-bit ``cls`` / ``reg`` / ``cls_output`` /
+    ``reg_output`` as they are (no cast in either direction) and return their
+    gradients in that type.  ``grad_scaler`` (a ``torch.amp.GradScaler``) makes
+    the step ``scaler.scale(total_loss).backward()``, ``scaler.step(optimizer)``,
+    ``scaler.update()``; without one the step is unchanged."""
+
+    def __init__(self, rpn, head, n_sample=(256, 128), optimizer=None, fused_losses=False, grad_scaler=None):
         self.rpn = rpn
         self.head = head
         self.n_sample = list(n_sample)
         self.optimizer = optimizer
         self.fused_losses = bool(fused_losses)
+        self.grad_scaler = grad_scaler
         self.last = {}
 
     def train_step(self, features, img_h, img_w, boxes, labels):
@@ -100,9 +108,15 @@ class Trainer:
             reg_loss = fast_rcnn_loc_loss(reg_output, reg_targets_classifier, cls_labels_classifier)
             cls_loss = F.cross_entropy(cls_output, cls_labels_classifier.long(), ignore_index=-1)
         total_loss = rpn_cls_loss + rpn_reg_loss + cls_loss + reg_loss
-        total_loss.backward()
-        if self.optimizer is not None:
-            self.optimizer.step()
+        if self.grad_scaler is not None:
+            self.grad_scaler.scale(total_loss).backward()
+            if self.optimizer is not None:
+                self.grad_scaler.step(self.optimizer)
+                self.grad_scaler.update()
+        else:
+            total_loss.backward()
+            if self.optimizer is not None:
+                self.optimizer.step()
         self.last = dict(cls=cls, reg=reg, rpn_labels=lab, rpn_reg_targets=reg_t, sample_rois=s_roi,
                          sample_reg=s_reg, sample_labels=s_lab, cls_output=cls_output,
                          reg_output=reg_output)
