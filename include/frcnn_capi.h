@@ -237,6 +237,69 @@ int frcnn_roi_pool_fwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W
 int frcnn_roi_pool_bwd_kernel_t(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW, char* name,
                                 size_t len);
 
+/* --------------------------------------------------------------- RoIAlign */
+
+/* torchvision.ops.roi_align(input, boxes, output_size, spatial_scale,
+ * sampling_ratio, aligned), forward and backward, with the semantics and the
+ * summation order of torchvision's CPU kernel (DESIGN.md §3 "RoIAlign").  No
+ * reference counterpart: the reference pools with roi_pool (nets/heads.py:48).
+ *   x, out, grad, grad_in: `dtype` (FRCNN_F32 / FRCNN_F16 / FRCNN_BF16), one per
+ *   call; x [N,C,H,W], out / grad [R,C,PH,PW], grad_in [N,C,H,W]
+ *   rois fp32 [R,5] = (b, x1, y1, x2, y2), any order
+ * Every operation is fp32 and separately rounded.  Per RoI:
+ *   off = aligned ? 0.5f : 0;  sw = x1*scale - off, sh = y1*scale - off,
+ *   ew = x2*scale - off, eh = y2*scale - off;  rw = ew - sw, rh = eh - sh, each
+ *   raised to 1.f when !aligned;  bh = rh / PH, bw = rw / PW;
+ *   gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / PH), gw likewise;
+ *   count = (float)max((int64)gh * gw, 1);
+ *   sample (ph, iy): y = (sh + ph*bh) + (((iy + .5f) * bh) / gh); x likewise from
+ *   sw, pw, bw, ix, gw.
+ * A sample with y < -1 || y > H || x < -1 || x > W is outside: it contributes
+ * nothing (forward) and adds nothing (backward).  Otherwise, per axis:
+ *   if (y <= 0) y = 0;  yl = (int)y;  if (yl >= H-1) { yh = yl = H-1; y = yl; }
+ *   else yh = yl + 1;  ly = y - yl, hy = 1 - ly
+ * and w1 = hy*hx, w2 = hy*lx, w3 = ly*hx, w4 = ly*lx.
+ * Forward: acc = +0; for iy, then ix, ascending:
+ *   acc += ((w1*v(yl,xl) + w2*v(yl,xh)) + w3*v(yh,xl)) + w4*v(yh,xh);
+ *   out[n,c,ph,pw] = acc / count.
+ * Backward: grad_in = +0; for n, ph, pw, iy, ix ascending and g = grad[n,c,ph,pw],
+ *   four additions in this order, all four even where a weight is zero:
+ *   gi[b,c,yl,xl] += (g*w1)/count; gi[b,c,yl,xh] += (g*w2)/count;
+ *   gi[b,c,yh,xl] += (g*w3)/count; gi[b,c,yh,xh] += (g*w4)/count
+ *   into fp32 sums in exactly this order: no atomics, the same bits on every call.
+ * Guards (torchvision's behaviour is undefined there): a RoI whose batch index
+ * b is not in (-1, N) (truncated toward zero otherwise), or one of whose four
+ * scaled coordinates x1*scale .. y2*scale is not finite or above 2^20 in
+ * magnitude, gives an all-zero output and no gradient; nothing is read or
+ * written out of bounds.
+ * sampling_ratio <= 0 is adaptive, 1..16 fixed, above 16 FRCNN_EINVAL.  Work per
+ * bin is bounded by the map, not by the box: samples outside the map (forward)
+ * or off the workgroup's pixels (backward) are skipped without being visited.
+ * 16-bit types: widened exactly at the load, the fp32 arithmetic above, rounded
+ * to nearest even once at the store (float16 overflow: +-inf); the backward
+ * never sums in 16 bits.
+ * Argument errors (FRCNN_EINVAL before any HIP call, the message names the
+ * argument): a dtype code other than the three, PH or PW < 1, sampling_ratio >
+ * 16, a null pointer with R > 0.  R == 0 succeeds; the backward then stores an
+ * all-zero grad_in.  The backward stores every grad_in element exactly once (no
+ * memset); one launch each.  Nothing is kept between launches: the workspace
+ * sizes are a nominal 256 and the buffers are not touched (NULL is accepted). */
+size_t frcnn_roi_align_fwd_workspace_size(int64_t R, int N, int C);
+int frcnn_roi_align_fwd_t(int dtype, const void* x, const float* rois, int64_t R, int N, int C, int H, int W,
+                          int PH, int PW, float spatial_scale, int sampling_ratio, int aligned, void* out,
+                          void* workspace, size_t ws_bytes, void* stream);
+size_t frcnn_roi_align_bwd_workspace_size(int64_t R, int N, int PH, int PW);
+int frcnn_roi_align_bwd_t(int dtype, const void* grad, const float* rois, int64_t R, int N, int C, int H, int W,
+                          int PH, int PW, float spatial_scale, int sampling_ratio, int aligned, void* grad_in,
+                          void* workspace, size_t ws_bytes, void* stream);
+/* The kernels the two calls launch for this dtype and shape, as their template
+ * names ("roi_align_fwd_kernel<ElemF16>", "roi_align_bwd_tile_kernel<ElemF32, 8>"),
+ * NUL-terminated in name[len].  Same argument checks as the calls. */
+int frcnn_roi_align_fwd_kernel(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                               int sampling_ratio, char* name, size_t len);
+int frcnn_roi_align_bwd_kernel(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
+                               int sampling_ratio, char* name, size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

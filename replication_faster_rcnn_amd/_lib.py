@@ -71,6 +71,12 @@ SIGNATURES = {
     "frcnn_roi_pool_fwd_head_t": (I32, [I32, P, P, P, I64, I32, I32, I32, I32, I32, I32, F32, F32, F32, I32,
                                         P, P, P, P, SZ, P]),
     "frcnn_roi_pool_bwd_t": (I32, [I32, P, P, P, I64, I32, I32, I32, I32, I32, I32, F32, P, P, SZ, P]),
+    "frcnn_roi_align_fwd_workspace_size": (SZ, [I64, I32, I32]),
+    "frcnn_roi_align_fwd_t": (I32, [I32, P, P, I64, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, P, SZ, P]),
+    "frcnn_roi_align_bwd_workspace_size": (SZ, [I64, I32, I32, I32]),
+    "frcnn_roi_align_bwd_t": (I32, [I32, P, P, I64, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, P, SZ, P]),
+    "frcnn_roi_align_fwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_roi_align_bwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),
@@ -296,6 +302,17 @@ def roi_pool_bwd_kernel(R, N, C, H, W, PH=7, PW=7, dtype=torch.float32) -> str:
     buf = ctypes.create_string_buffer(160)
     check(lib.frcnn_roi_pool_bwd_kernel_t(dtype_code(dtype), int(R), int(N), int(C), int(H), int(W), int(PH),
                                           int(PW), buf, 160), "roi_pool_bwd_kernel")
+    return buf.value.decode()
+
+
+def roi_align_kernel(which: str, R, N, C, H, W, PH=7, PW=7, sampling_ratio=-1, dtype=torch.float32) -> str:
+    """frcnn_roi_align_fwd_kernel / _bwd_kernel (``which`` = "fwd" | "bwd"): the template
+    name of the RoIAlign kernel a call of this shape and dtype launches.  Host only."""
+    lib = load(require_gpu=False)
+    buf = ctypes.create_string_buffer(160)
+    fn = {"fwd": lib.frcnn_roi_align_fwd_kernel, "bwd": lib.frcnn_roi_align_bwd_kernel}[which]
+    check(fn(dtype_code(dtype), int(R), int(N), int(C), int(H), int(W), int(PH), int(PW), int(sampling_ratio), buf,
+             160), f"roi_align_{which}_kernel")
     return buf.value.decode()
 
 

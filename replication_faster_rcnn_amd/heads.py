@@ -9,6 +9,11 @@ avgpool) and the two FCs stay plain PyTorch (not the target).
 float16 / bfloat16 features (a backbone under ``torch.autocast``) are pooled
 in their own type: ``cropped`` reaches the classifier in ``x``'s dtype and
 ``x.grad`` comes back in it, with no widening cast on either side.
+
+``ResnetHead(..., pool="align")`` (an extension; the default "max" is the path
+above, unchanged) pools with ``ops.roi_align`` instead: ``ops.roi_transform``,
+then RoIAlign forward and its deterministic HIP backward (DESIGN.md §3
+"RoIAlign"), in ``x``'s dtype as well.
 """
 from __future__ import annotations
 
@@ -19,8 +24,17 @@ from . import _lib, ops
 
 
 class ResnetHead(nn.Module):
-    def __init__(self, classifier, roi_size=7, spatial_scale=1, n_classes=21):
+    def __init__(self, classifier, roi_size=7, spatial_scale=1, n_classes=21, pool="max", sampling_ratio=-1,
+                 aligned=False):
+        """``pool`` (extension): "max" is the reference's ``roi_pool``; "align" pools with
+        ``ops.roi_align`` (``sampling_ratio``, ``aligned`` as torchvision's) on the same
+        transformed boxes."""
         super().__init__()
+        if pool not in ("max", "align"):
+            raise ValueError(f"ResnetHead: pool must be 'max' or 'align'; got {pool!r}")
+        self.pool = pool
+        self.sampling_ratio = sampling_ratio
+        self.aligned = aligned
         self.classifier = classifier
         self.reg = nn.Linear(in_features=512, out_features=n_classes * 4)
         self.cls = nn.Linear(in_features=512, out_features=n_classes)
@@ -43,8 +57,13 @@ class ResnetHead(nn.Module):
         r = torch.as_tensor(rois).detach().to(dev, torch.float32).contiguous()
         ri = torch.as_tensor(roi_inds).detach().to(dev, torch.float32).contiguous()
         out_dev = x.device
-        cropped = ops.roi_pool_head(x, r, ri, (self.roi_size, self.roi_size), img_h, img_w,
-                                    self.spatial_scale, rois_sorted=bool(rois_sorted))[0].to(out_dev)
+        if self.pool == "align":
+            boxes = ops.roi_transform(r, ri, img_h, img_w, x.shape[2], x.shape[3])
+            cropped = ops.roi_align(x, boxes, (self.roi_size, self.roi_size), self.spatial_scale,
+                                    self.sampling_ratio, self.aligned)
+        else:
+            cropped = ops.roi_pool_head(x, r, ri, (self.roi_size, self.roi_size), img_h, img_w,
+                                        self.spatial_scale, rois_sorted=bool(rois_sorted))[0].to(out_dev)
         fc6 = self.classifier(cropped)
         fc6 = fc6.view(fc6.shape[0], -1)
         reg = self.reg(fc6)

@@ -6,6 +6,11 @@
   roi_pool`` as called at nets/heads.py:48, with an autograd backward (the
   reference reaches torchvision's ``_roi_pool_backward`` from
   ``total_loss.backward()`` at train.py:126).
+* ``roi_align(input, boxes, output_size, spatial_scale, sampling_ratio,
+  aligned)`` -- ``torchvision.ops.roi_align`` with the semantics and summation
+  order of torchvision's CPU kernel, forward and a deterministic backward (no
+  reference counterpart: the RoI feature extractor users swap in for
+  ``roi_pool``; DESIGN.md §3 "RoIAlign").
 * ``propose(...)`` -- the batched proposal layer (nets/rpn.py:47-79 over all
   images at once, replacing the per-image loop nets/rpn.py:131-136).
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
@@ -25,12 +30,13 @@
 Two input rules (tests/test_gpu_wrapper_inputs.py):
 
 * The reference-signature drop-ins (``nms``, ``roi_pool*``, ``roi_pool_head``,
-  ``rpn_head_epilogue``) convert whatever they are given: inputs may live on the
-  CPU (reference style), be strided views or another float type; they are moved
-  to the current HIP device as contiguous fp32, and results are returned on the
-  input's device.  They raise only on shapes that do not belong together.
+  ``roi_align``, ``rpn_head_epilogue``) convert whatever they are given: inputs
+  may live on the CPU (reference style), be strided views or another float type;
+  they are moved to the current HIP device as contiguous fp32, and results are
+  returned on the input's device.  They raise only on shapes that do not belong
+  together (``roi_align`` also on a ``sampling_ratio`` above 16).
   One exception keeps its type: a float16 or bfloat16 ``input`` of ``roi_pool``,
-  ``roi_pool_with_argmax`` and ``roi_pool_head`` (a backbone under autocast) is
+  ``roi_pool_with_argmax``, ``roi_pool_head`` and ``roi_align`` (a backbone under autocast) is
   moved or made contiguous if needed but never widened, the pooled output and
   the gradient have the input's dtype as torchvision's do, and the kernels
   read and write the 16-bit values directly (DESIGN.md §3 "RoIPool in 16-bit
@@ -288,6 +294,92 @@ def roi_pool(input: torch.Tensor, boxes, output_size, spatial_scale: float = 1.0
              rois_sorted=None) -> torch.Tensor:
     """torchvision.ops.roi_pool (nets/heads.py:48)."""
     return roi_pool_with_argmax(input, boxes, output_size, spatial_scale, rois_sorted)[0]
+
+
+# ----------------------------------------------------------------- roi_align
+ROI_ALIGN_MAX_SAMPLING_RATIO = 16
+
+
+def _roi_align_fwd(x: torch.Tensor, rois: torch.Tensor, ph: int, pw: int, ss: float, sr: int, aligned: bool):
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    R = rois.size(0)
+    code = _POOL_DTYPE_CODE.get(x.dtype)
+    if code is None:
+        raise _pool_dtype_error("roi_align forward", x.dtype)
+    out = torch.empty((R, C, ph, pw), dtype=x.dtype, device=x.device)
+    _lib.check(lib.frcnn_roi_align_fwd_t(code, _lib.ptr(x), _lib.ptr(rois), R, N, C, H, W, ph, pw, float(ss), int(sr),
+                                         int(bool(aligned)), _lib.ptr(out), None, 0, _lib.stream_ptr()),
+               "roi_align forward")
+    return out
+
+
+def _roi_align_bwd(grad: torch.Tensor, rois: torch.Tensor, shape, ss: float, sr: int, aligned: bool):
+    lib = _lib.load()
+    N, C, H, W = shape
+    R, _, ph, pw = grad.shape
+    code = _POOL_DTYPE_CODE.get(grad.dtype)
+    if code is None:
+        raise _pool_dtype_error("roi_align backward", grad.dtype)
+    gi = torch.empty((N, C, H, W), dtype=grad.dtype, device=grad.device)
+    _lib.check(lib.frcnn_roi_align_bwd_t(code, _lib.ptr(grad), _lib.ptr(rois), R, N, C, H, W, ph, pw, float(ss),
+                                         int(sr), int(bool(aligned)), _lib.ptr(gi), None, 0, _lib.stream_ptr()),
+               "roi_align backward")
+    return gi
+
+
+class _RoIAlignFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rois, ph, pw, ss, sr, aligned):
+        out = _roi_align_fwd(x, rois, ph, pw, ss, sr, aligned)
+        ctx.save_for_backward(rois)
+        ctx.meta = (tuple(x.shape), ph, pw, ss, sr, aligned, x.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (rois,) = ctx.saved_tensors
+        shape, ph, pw, ss, sr, aligned, dtype = ctx.meta
+        gi = _roi_align_bwd(_pool_grad(grad_out, dtype), rois, shape, ss, sr, aligned)
+        return gi, None, None, None, None, None, None
+
+
+def roi_align(input: torch.Tensor, boxes, output_size, spatial_scale: float = 1.0, sampling_ratio: int = -1,
+              aligned: bool = False) -> torch.Tensor:
+    """torchvision.ops.roi_align with the semantics and the summation order of
+    torchvision's CPU kernel, forward and backward (frcnn_roi_align_fwd_t /
+    _bwd_t; DESIGN.md §3 "RoIAlign" is the contract): bilinear samples on a
+    ``sampling_ratio`` x ``sampling_ratio`` grid per bin (<= 0: adaptive,
+    ceil(bin size); at most 16), averaged.  ``boxes`` is [K, 5] (batch_idx, x1,
+    y1, x2, y2) or a list of [L, 4] tensors, in any order.  The gradient is
+    deterministic and bit-equal to the CPU order of additions (torchvision's
+    own GPU backward is neither).
+
+    A reference-signature drop-in, with ``roi_pool``'s input rule: host, strided
+    or other float inputs are converted and the result comes back on the
+    input's device; a float16 / bfloat16 ``input`` is never widened and ``out``
+    and the gradient have its dtype.  RoIs with a batch index outside [0, N) or
+    a scaled coordinate that is not finite or beyond 2^20 give zeros and no
+    gradient."""
+    if not isinstance(input, torch.Tensor) or input.dim() != 4:
+        raise RuntimeError("input must be [N, C, H, W]")
+    try:
+        ph, pw = (output_size, output_size) if isinstance(output_size, int) else (int(v) for v in output_size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"roi_align: output_size must be an int or (h, w); got {output_size!r}") from None
+    if isinstance(boxes, (list, tuple)):
+        if len(boxes) != input.size(0):
+            raise RuntimeError(f"roi_align: a list of boxes needs one entry per image; got {len(boxes)} for "
+                               f"{input.size(0)} images")
+        if any(not isinstance(b, torch.Tensor) or b.dim() != 2 or b.size(1) != 4 for b in boxes):
+            raise RuntimeError("roi_align: every entry of a list of boxes must be a [L, 4] tensor")
+    out_dev = input.device
+    x = _pool_input(input)  # differentiable move, so CPU leaf tensors get their grad
+    rois = _to_dev(_boxes_to_rois(boxes))
+    out = _RoIAlignFunction.apply(x, rois, int(ph), int(pw), float(spatial_scale), int(sampling_ratio),
+                                  bool(aligned))
+    return out.to(out_dev)
 
 
 # ------------------------------------------------------------------ proposals
