@@ -495,6 +495,48 @@ int frcnn_eval_ap(int C, int64_t n_records, const int64_t* hdr, const uint64_t* 
                   const int8_t* rec_flag, int use_07_metric, double* ap, double* map,
                   uint64_t* sorted_key, void* ws, size_t ws_bytes, void* stream);
 
+/* COCO-style evaluation (DESIGN.md "COCO-style evaluation" is the contract:
+ * pycocotools.cocoeval with iouType "bbox", restated; no reference counterpart).
+ * One batch is matched at the ten IoU thresholds and the four area ranges and
+ * appended to a device-resident accumulator.  Inputs and limits are those of
+ * frcnn_eval_update, with gt_crowd uint8 [N,G] or NULL (none) as the one gt flag
+ * (pycocotools' iscrowd; a caller who wants VOC's difficult objects treated as
+ * ignore regions passes them here).
+ *   tables    double [119], device: the IoU thresholds T[10], the recall
+ *             thresholds R[101], the area ranges A[4][2] (lo, hi; both ends
+ *             inclusive) in the order all, small, medium, large.  They are read,
+ *             never recomputed.
+ * State (caller-owned, hdr all zero = empty):
+ *   hdr       int64 [4+4C]   n_records, n_images, batches dropped, 0, npig[C][4]
+ *   rec_key   uint64 [cap]   class << 56 | desc_score_key(score) << 24 | record index
+ *   rec_bits  uint64 [cap][2], 16-byte aligned (as det_boxes is: both are read 16 bytes at a time)
+ *             word 0: bits 20a..20a+9 the matched mask (bit = threshold) and bits
+ *             20a+10..20a+19 the ignored mask of area range a = 0, 1, 2
+ *             word 1: bits 0..9 / 10..19 those masks of area range 3; bits 32..38
+ *             the rank within (image, class) by (descending score, slot), 127 for
+ *             a rank >= 100 and for class 0 records
+ * Every slot below the clamped count becomes one record in (image, slot) order;
+ * a batch that does not fit in cap writes nothing and adds one to hdr[2]. */
+int frcnn_coco_eval_update(int N, int M, int G, int C, int64_t cap, const float* det_boxes,
+                           const int32_t* det_labels, const float* det_scores, const int32_t* det_count,
+                           const double* gt_boxes, const int32_t* gt_labels, const uint8_t* gt_crowd,
+                           const double* tables, int64_t* hdr, uint64_t* rec_key, uint64_t* rec_bits,
+                           void* stream);
+
+/* pycocotools' accumulate() and summarize() of an accumulator (once per
+ * dataset).  n_records is hdr[0], read back by the caller; the keys are sorted
+ * inside the library (frcnn_eval_ap's sort).  Outputs, device, C-contiguous:
+ *   precision double [10,101,C,4,3], recall double [10,C,4,3]  (-1: no gt)
+ *   stats double [12]: AP AP50 AP75 APs APm APl AR1 AR10 AR100 ARs ARm ARl
+ *   ap_per_class double [C]: AP of one class over all areas at maxDet 100
+ * Workspace: frcnn_coco_eval_workspace_size(C, cap) bytes serve every n_records
+ * <= cap (0 for a C or cap outside the limits). */
+size_t frcnn_coco_eval_workspace_size(int C, int64_t cap);
+int frcnn_coco_eval_accumulate(int C, int64_t n_records, const int64_t* hdr, const uint64_t* rec_key,
+                               const uint64_t* rec_bits, const double* tables, double* precision,
+                               double* recall, double* stats, double* ap_per_class, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ losses */
 
 /* The training losses of one stage, train.py:29-57 with :81-83 (RPN) or

@@ -104,6 +104,9 @@ SIGNATURES = {
     "frcnn_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, F64, I32, P, P, P, P, P]),
     "frcnn_eval_ap_workspace_size": (SZ, [I32, I64]),
     "frcnn_eval_ap": (I32, [I32, I64, P, P, P, I32, P, P, P, P, SZ, P]),
+    "frcnn_coco_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "frcnn_coco_eval_workspace_size": (SZ, [I32, I64]),
+    "frcnn_coco_eval_accumulate": (I32, [I32, I64, P, P, P, P, P, P, P, P, P, SZ, P]),
     "frcnn_losses_workspace_size": (SZ, [I64, I32]),
     "frcnn_losses_fwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, SZ, P]),
     "frcnn_losses_bwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),

@@ -29,26 +29,15 @@
 //                         first with running tp / fp, suffix maximum of the
 //                         precision and the integration.
 //   eval_map_kernel     : mean of the non-NaN APs in ascending class order.
+// The limits, the header step and the sort's host entry (eval_sort_keys) are
+// shared with the COCO-style evaluation (eval_common.h, eval_coco.hip).
 // Integer atomics only (LDS claim minima, npos counts): every result is
 // independent of the order workgroups and waves run in.
 #include <cmath>
 
-#include "common.h"
+#include "eval_common.h"
 
 namespace frcnn {
-
-constexpr int kEvMaxN = 1024;
-constexpr int kEvMaxM = 1 << 20;
-constexpr int kEvMaxG = 256;
-constexpr int kEvMaxC = 128;
-constexpr int64_t kEvMaxCap = int64_t{1} << 24;  // the record index is a 24-bit key field
-constexpr int kEvThreads = 256;
-constexpr int kEvWaves = kEvThreads / kWave;
-
-__device__ __forceinline__ int ev_count(const int32_t* det_count, int n, int M) {
-    const int k = det_count[n];
-    return k < 0 ? 0 : (k > M ? M : k);
-}
 
 // np.maximum / np.minimum (NaN propagates), as bbox_iou uses them.
 __device__ __forceinline__ double ev_max(double a, double b) { return (a != a || a >= b) ? a : b; }
@@ -97,44 +86,6 @@ __device__ __forceinline__ int ev_best_gt(const float* db, int label, int G, con
         }
     }
     return (ovmax > thr) ? jmax : -1;
-}
-
-__device__ __forceinline__ long long ev_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum of the clamped counts of all images (total) and of the images before n.
-__device__ __forceinline__ void ev_count_sums(const int32_t* det_count, int N, int M, int n, long long* red,
-                                              long long* before, long long* total) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    long long b = 0, t = 0;
-    for (int i = tid; i < N; i += kEvThreads) {
-        const int k = ev_count(det_count, i, M);
-        t += k;
-        b += i < n ? k : 0;
-    }
-    b = ev_wave_sum(b);
-    t = ev_wave_sum(t);
-    if (lane == 0) {
-        red[wid] = b;
-        red[kEvWaves + wid] = t;
-    }
-    __syncthreads();
-    b = t = 0;
-    for (int w = 0; w < kEvWaves; ++w) {
-        b += red[w];
-        t += red[kEvWaves + w];
-    }
-    __syncthreads();
-    *before = b;
-    *total = t;
-}
-
-// A batch that does not fit (or a header that is not a state of this capacity)
-// writes nothing.
-__device__ __forceinline__ bool ev_fits(long long nrec, long long total, long long cap) {
-    return nrec >= 0 && nrec <= cap && total <= cap - nrec;
 }
 
 __global__ __launch_bounds__(kEvThreads) void eval_match_kernel(
@@ -226,16 +177,7 @@ __global__ __launch_bounds__(kEvThreads) void eval_advance_kernel(int N, int M, 
                                                                   const int32_t* __restrict__ det_count,
                                                                   long long* hdr) {
     __shared__ long long red[2 * kEvWaves];
-    long long before, total;
-    ev_count_sums(det_count, N, M, 0, red, &before, &total);
-    if (threadIdx.x == 0) {
-        if (ev_fits(hdr[0], total, cap)) {
-            hdr[0] += total;
-            hdr[1] += N;
-        } else {
-            hdr[2] += 1;
-        }
-    }
+    ev_advance(N, M, cap, det_count, hdr, red);
 }
 
 // ----------------------------------------------------------------------- sort
@@ -331,15 +273,6 @@ __global__ __launch_bounds__(kEvThreads) void eval_sort_scatter_kernel(const uin
 }
 
 // ------------------------------------------------------------------------- AP
-__device__ __forceinline__ int ev_lower_bound(const uint64_t* __restrict__ keys, int n, uint64_t v) {
-    int lo = 0, hi = n;  // first index with keys[i] >= v
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // The flag of a sorted key's record.  A record index is below n by construction;
 // a key that is not one (a caller's n over the records held) reads as ignored.
 __device__ __forceinline__ int ev_flag(const int8_t* __restrict__ rec_flag, uint64_t key, int n) {
@@ -491,6 +424,34 @@ static EvalWs carve_eval(void* ws, int64_t cap) {
     return w;
 }
 
+size_t eval_sort_workspace_size(int64_t cap) { return carve_eval(nullptr, cap).bytes; }
+
+int eval_sort_keys(const uint64_t* rec_key, int64_t n_records, void* ws, size_t ws_bytes, const char* who,
+                   hipStream_t st, const uint64_t** sorted) {
+    const int n = static_cast<int>(n_records);
+    const EvalWs w = carve_eval(ws, n_records);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("%s: workspace %zu < %zu", who, ws ? ws_bytes : size_t{0}, w.bytes);
+        return FRCNN_EWORKSPACE;
+    }
+    const int nblk = sort_blocks(n_records);
+    const uint64_t* src = rec_key;
+    uint64_t* dst = w.a;
+    for (int pass = 0; pass < kSortPasses; ++pass) {
+        const int shift = kSortFirstBit + pass * kSortBits;
+        eval_sort_hist_kernel<<<nblk, kEvThreads, 0, st>>>(src, n, shift, nblk, w.hist);
+        FRCNN_LAUNCH_CHECK("eval_sort_hist_kernel");
+        eval_sort_scan_kernel<<<1, kScanThreads, 0, st>>>(w.hist, kSortBins * nblk);
+        FRCNN_LAUNCH_CHECK("eval_sort_scan_kernel");
+        eval_sort_scatter_kernel<<<nblk, kEvThreads, 0, st>>>(src, dst, n, shift, nblk, w.hist);
+        FRCNN_LAUNCH_CHECK("eval_sort_scatter_kernel");
+        src = dst;
+        dst = dst == w.a ? w.b : w.a;
+    }
+    *sorted = src;  // an odd number of passes: w.a
+    return FRCNN_OK;
+}
+
 }  // namespace frcnn
 
 using namespace frcnn;
@@ -540,26 +501,8 @@ extern "C" int frcnn_eval_ap(int C, int64_t n_records, const int64_t* hdr, const
     const int n = static_cast<int>(n_records);
     const uint64_t* sorted = nullptr;
     if (n > 0) {
-        const EvalWs w = carve_eval(ws, n_records);
-        if (!ws || ws_bytes < w.bytes) {
-            set_error("frcnn_eval_ap: workspace %zu < %zu", ws ? ws_bytes : size_t{0}, w.bytes);
-            return FRCNN_EWORKSPACE;
-        }
-        const int nblk = sort_blocks(n_records);
-        const uint64_t* src = rec_key;
-        uint64_t* dst = w.a;
-        for (int pass = 0; pass < kSortPasses; ++pass) {
-            const int shift = kSortFirstBit + pass * kSortBits;
-            eval_sort_hist_kernel<<<nblk, kEvThreads, 0, st>>>(src, n, shift, nblk, w.hist);
-            FRCNN_LAUNCH_CHECK("eval_sort_hist_kernel");
-            eval_sort_scan_kernel<<<1, kScanThreads, 0, st>>>(w.hist, kSortBins * nblk);
-            FRCNN_LAUNCH_CHECK("eval_sort_scan_kernel");
-            eval_sort_scatter_kernel<<<nblk, kEvThreads, 0, st>>>(src, dst, n, shift, nblk, w.hist);
-            FRCNN_LAUNCH_CHECK("eval_sort_scatter_kernel");
-            src = dst;
-            dst = dst == w.a ? w.b : w.a;
-        }
-        sorted = src;  // an odd number of passes: w.a
+        const int rc = eval_sort_keys(rec_key, n_records, ws, ws_bytes, "frcnn_eval_ap", st, &sorted);
+        if (rc) return rc;
         if (sorted_key && hipMemcpyAsync(sorted_key, sorted, sizeof(uint64_t) * static_cast<size_t>(n),
                                          hipMemcpyDeviceToDevice, st) != hipSuccess)
             return check_launch("frcnn_eval_ap: copy of the sorted keys");

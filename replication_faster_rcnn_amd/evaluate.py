@@ -1,4 +1,4 @@
-"""PASCAL VOC evaluation of the detector on the device.
+"""PASCAL VOC and COCO-style evaluation of the detector on the device.
 
 The reference stops before this stage (its ``test_eval.py`` is an empty
 file); the protocol is the VOC devkit's ``voc_eval``, stated as a contract in
@@ -12,6 +12,11 @@ allocation, no host read -- and ``result`` closes the dataset with
         model.predict(x, width, height)
         ev.update(model.last_detections, gt_boxes, gt_labels, gt_difficult)
     print(ev.result()["map"])
+
+``COCOEvaluator`` has the same shape for the COCO protocol (DESIGN.md
+"COCO-style evaluation"): AP averaged over IoU 0.50:0.05:0.95, AP50, AP75, AP
+for small / medium / large objects and AR at 1 / 10 / 100 detections per image,
+on ``ops.coco_eval_update`` and ``ops.coco_eval_accumulate``.
 """
 from __future__ import annotations
 
@@ -75,3 +80,62 @@ class VOCEvaluator:
         ap, mean = ops.eval_ap(self.state, int(hdr[0]), use_07_metric=self.use_07_metric)
         return dict(ap=ap.cpu().numpy(), map=float(mean.item()), npos=hdr[4:].copy(), n_records=int(hdr[0]),
                     n_images=int(hdr[1]))
+
+
+COCO_STATS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+
+
+class COCOEvaluator:
+    """Accumulates, for every detection, its rank within (image, class) and
+    whether it is matched / ignored at each of the ten IoU thresholds and four
+    area ranges of the COCO protocol, in device arrays of ``capacity`` records
+    (``ops.coco_eval_state``), for ``n_class`` classes with class 0 the
+    background."""
+
+    def __init__(self, n_class: int = 21, capacity: int = 1 << 20):
+        self.n_class = int(n_class)
+        self.capacity = int(capacity)
+        self.state = ops.coco_eval_state(self.n_class, self.capacity)
+
+    def reset(self) -> None:
+        """Back to the empty state (the record arrays need no clearing)."""
+        self.state[0].zero_()
+
+    def update(self, det, gt_boxes, gt_labels, gt_crowd=None) -> None:
+        """One batch.  ``det``: the tuple ``ops.detect`` returns or
+        ``FasterRCNN.last_detections``.  gt as the loader yields it: boxes
+        [N, G, 4] and labels [N, G] of any real dtype (rows outside
+        1..n_class-1, such as the loader's -1 padding, are no gt), ``gt_crowd``
+        [N, G] or None -- the one gt flag (``ops.coco_eval_update``); pass the
+        loader's ``gt_difficult`` to have VOC's difficult objects ignored.
+        numpy arrays and CPU tensors are moved to the device.  Nothing is read
+        back."""
+        if len(det) == 6:
+            det = (det[0], det[1], det[2], det[4])
+        if len(det) != 4:
+            raise RuntimeError("COCOEvaluator.update: det must be ops.detect's 6-tuple or (boxes, labels, scores, "
+                               "count)")
+        det = tuple(_dev(t, dt) for t, dt in zip(det, (torch.float32, torch.int32, torch.float32, torch.int32)))
+        ops.coco_eval_update(det, _dev(gt_boxes, torch.float64), _dev(gt_labels, torch.int32),
+                             None if gt_crowd is None else _dev(gt_crowd, torch.uint8), state=self.state)
+
+    def result(self) -> dict:
+        """{"stats": fp64 [12] in pycocotools' order, each of them by name ("AP",
+        "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm",
+        "ARl"), "ap_per_class": fp64 [n_class], "precision": fp64 [10, 101,
+        n_class, 4, 3], "recall": fp64 [10, n_class, 4, 3], "npig": int64
+        [n_class, 4], "n_records", "n_images"}; -1 where there is no gt.  The only
+        synchronisation.  Raises ``FrcnnError`` when a batch was dropped because
+        the capacity was too small: the numbers would be of a part of the
+        dataset."""
+        hdr = self.state[0].cpu().numpy()
+        if hdr[2] != 0:
+            raise _lib.FrcnnError(f"COCOEvaluator: {int(hdr[2])} batch(es) did not fit in capacity={self.capacity} "
+                                  f"({int(hdr[0])} records held) and were dropped; use a larger capacity")
+        precision, recall, stats, apc = ops.coco_eval_accumulate(self.state, int(hdr[0]))
+        stats = stats.cpu().numpy()
+        out = dict(stats=stats, ap_per_class=apc.cpu().numpy(), precision=precision.cpu().numpy(),
+                   recall=recall.cpu().numpy(), npig=hdr[4:].reshape(self.n_class, 4).copy(),
+                   n_records=int(hdr[0]), n_images=int(hdr[1]))
+        out.update({name: float(v) for name, v in zip(COCO_STATS, stats)})
+        return out

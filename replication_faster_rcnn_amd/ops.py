@@ -19,6 +19,9 @@
 * ``eval_update(...)`` / ``eval_ap(...)`` -- PASCAL VOC evaluation of those
   detections against ground truth on the device (no reference counterpart:
   its test_eval.py is empty; DESIGN.md "Evaluation").
+* ``coco_eval_update(...)`` / ``coco_eval_accumulate(...)`` -- the COCO protocol
+  on the same inputs: AP over IoU 0.50:0.95, by object size, AR at 1 / 10 / 100
+  detections (DESIGN.md "COCO-style evaluation").
 * ``rpn_losses(...)`` / ``head_losses(...)`` -- the four training losses of
   train.py:29-57, :81-83, :112-121, fused, with their own backward (DESIGN.md
   "Losses").
@@ -44,7 +47,7 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
 * The hot-path ops on device tensors (``propose``, ``roi_transform``,
-  ``detect``, ``eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
+  ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
@@ -631,6 +634,124 @@ def eval_ap(state, n_records: int = None, *, use_07_metric: bool = False, return
                                  _lib.ptr(ap), _lib.ptr(mean), _lib.ptr(skey) if n else None, _lib.ptr(ws),
                                  ws.numel(), _lib.stream_ptr()), "eval_ap")
     return (ap, mean, skey) if return_sorted else (ap, mean)
+
+
+# ------------------------------------------------------ COCO-style evaluation
+def coco_eval_tables():
+    """The constants of the COCO protocol as the one fp64 [119] table the kernels
+    read: IoU thresholds T[10], recall thresholds R[101], area ranges A[4][2]
+    (all, small, medium, large; both ends inclusive).  Host tensor."""
+    import numpy as np
+    t = np.linspace(.5, .95, 10)
+    r = np.linspace(0, 1, 101)
+    a = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], np.float64)
+    return torch.from_numpy(np.concatenate([t, r, a.reshape(-1)]))
+
+
+def coco_eval_state(n_class: int, capacity: int, device=None):
+    """An empty COCO-style accumulator (DESIGN.md "COCO-style evaluation"): (hdr
+    int64 [4 + 4 * n_class] zeroed, rec_key int64 [capacity], rec_bits int64
+    [capacity, 2] -- the C-ABI's uint64 words --, tables fp64 [119]) on the device."""
+    _lib.load()
+    if not 2 <= int(n_class) <= 128 or not 1 <= int(capacity) <= EVAL_MAX_CAPACITY:
+        raise RuntimeError(f"coco_eval_state: n_class={n_class} must be in [2, 128] and capacity={capacity} in "
+                           f"[1, {EVAL_MAX_CAPACITY}]")
+    dev = _lib.device() if device is None else device
+    return (torch.zeros(4 + 4 * int(n_class), dtype=torch.int64, device=dev),
+            torch.empty(int(capacity), dtype=torch.int64, device=dev),
+            torch.empty((int(capacity), 2), dtype=torch.int64, device=dev),
+            coco_eval_tables().to(dev))
+
+
+def _coco_state_check(state, what):
+    want = (torch.int64, torch.int64, torch.int64, torch.float64)
+    if len(state) != 4 or any(not isinstance(t, torch.Tensor) or t.dtype != d or not t.is_cuda
+                              or not t.is_contiguous() for t, d in zip(state, want)):
+        raise RuntimeError(f"{what}: state must be ops.coco_eval_state's (hdr int64, rec_key int64, rec_bits int64, "
+                           "tables float64) device tensors")
+    hdr, key, bits, tables = state
+    if (hdr.dim() != 1 or hdr.numel() < 12 or (hdr.numel() - 4) % 4 or key.dim() != 1 or key.numel() < 1
+            or tuple(bits.shape) != (key.numel(), 2) or tuple(tables.shape) != (119,)):
+        raise RuntimeError(f"{what}: state arrays of shapes {tuple(hdr.shape)} / {tuple(key.shape)} / "
+                           f"{tuple(bits.shape)} / {tuple(tables.shape)} do not belong together")
+    return (hdr.numel() - 4) // 4, key.numel()
+
+
+def coco_eval_update(det, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_crowd: torch.Tensor = None, *,
+                     state) -> None:
+    """Match one batch of detections against its ground truth at the ten IoU
+    thresholds and four area ranges of the COCO protocol and append the records
+    to ``state`` (frcnn_coco_eval_update; DESIGN.md "COCO-style evaluation" is the
+    contract) -- stream-ordered, no allocation, no host synchronisation.
+
+    ``det`` is the tuple ``ops.detect`` returns (or ``(det_boxes, det_labels,
+    det_scores, det_count)``); gt_boxes fp64 [N, G, 4] as [ymin, xmin, ymax,
+    xmax], gt_labels int32 [N, G] (valid rows: 1..n_class-1), gt_crowd uint8
+    [N, G] or None; all contiguous device tensors.  ``gt_crowd`` is the one gt
+    flag, as in pycocotools, where ``iscrowd`` overwrites ``ignore``: a flagged gt
+    is an ignore region that any number of detections may match (IoU over the
+    detection's area), and it counts as no positive.  Pass VOC's
+    ``gt_difficult`` there to have difficult objects treated that way.  A batch
+    that does not fit in the state's capacity is dropped as a whole and counted
+    in hdr[2]."""
+    lib = _lib.load()
+    if len(det) == 6:
+        boxes, labels, scores, _, count, _ = det
+    elif len(det) == 4:
+        boxes, labels, scores, count = det
+    else:
+        raise RuntimeError("coco_eval_update: det must be ops.detect's 6-tuple or (boxes, labels, scores, count)")
+    ins = [("det_boxes", boxes, torch.float32), ("det_labels", labels, torch.int32),
+           ("det_scores", scores, torch.float32), ("det_count", count, torch.int32),
+           ("gt_boxes", gt_boxes, torch.float64), ("gt_labels", gt_labels, torch.int32)]
+    if gt_crowd is not None:
+        ins.append(("gt_crowd", gt_crowd, torch.uint8))
+    for name, t, dt in ins:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError(f"coco_eval_update: {name} must be a contiguous {dt} device tensor")
+    C, cap = _coco_state_check(state, "coco_eval_update")
+    if labels.dim() != 2 or gt_labels.dim() != 2:
+        raise RuntimeError("coco_eval_update: det_labels must be [N, M] and gt_labels [N, G]")
+    N, M = labels.shape
+    G = gt_labels.shape[1]
+    if (tuple(boxes.shape) != (N, M, 4) or tuple(scores.shape) != (N, M) or tuple(count.shape) != (N,)
+            or tuple(gt_boxes.shape) != (N, G, 4) or gt_labels.shape[0] != N
+            or (gt_crowd is not None and tuple(gt_crowd.shape) != (N, G))):
+        raise RuntimeError(f"coco_eval_update: det {tuple(boxes.shape)} / {tuple(labels.shape)} / "
+                           f"{tuple(scores.shape)} / {tuple(count.shape)} and gt {tuple(gt_boxes.shape)} / "
+                           f"{tuple(gt_labels.shape)} do not match")
+    hdr, key, bits, tables = state
+    _lib.check(lib.frcnn_coco_eval_update(N, M, G, C, cap, _lib.ptr(boxes), _lib.ptr(labels), _lib.ptr(scores),
+                                          _lib.ptr(count), _lib.ptr(gt_boxes), _lib.ptr(gt_labels),
+                                          _lib.ptr(gt_crowd), _lib.ptr(tables), _lib.ptr(hdr), _lib.ptr(key),
+                                          _lib.ptr(bits), _lib.stream_ptr()), "coco_eval_update")
+
+
+def coco_eval_accumulate(state, n_records: int = None, *, workspace=None):
+    """pycocotools' accumulate() and summarize() of an accumulator
+    (frcnn_coco_eval_accumulate): (precision fp64 [10, 101, C, 4, 3], recall fp64
+    [10, C, 4, 3], stats fp64 [12], ap_per_class fp64 [C]) device tensors; -1
+    where there is no gt.  ``n_records`` is hdr[0]; when it is not given it is
+    read from the device (a host synchronisation)."""
+    lib = _lib.load()
+    C, cap = _coco_state_check(state, "coco_eval_accumulate")
+    hdr, key, bits, tables = state
+    n = int(hdr[0].item()) if n_records is None else int(n_records)
+    if not 0 <= n <= cap:
+        raise RuntimeError(f"coco_eval_accumulate: n_records={n} outside the state's capacity {cap}")
+    dev = hdr.device
+    precision = torch.empty((10, 101, C, 4, 3), dtype=torch.float64, device=dev)
+    recall = torch.empty((10, C, 4, 3), dtype=torch.float64, device=dev)
+    stats = torch.empty(12, dtype=torch.float64, device=dev)
+    apc = torch.empty(C, dtype=torch.float64, device=dev)
+    need = int(lib.frcnn_coco_eval_workspace_size(C, max(n, 1)))
+    ws = workspace if workspace is not None else _lib.cached_workspace("coco_eval", need, dev)
+    if ws.numel() < need:
+        raise RuntimeError(f"coco_eval_accumulate: workspace of {ws.numel()} B < {need} B")
+    _lib.check(lib.frcnn_coco_eval_accumulate(C, n, _lib.ptr(hdr), _lib.ptr(key), _lib.ptr(bits), _lib.ptr(tables),
+                                              _lib.ptr(precision), _lib.ptr(recall), _lib.ptr(stats), _lib.ptr(apc),
+                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "coco_eval_accumulate")
+    return precision, recall, stats, apc
 
 
 # ------------------------------------------------------------- RPN epilogue
