@@ -300,6 +300,55 @@ int frcnn_roi_align_fwd_kernel(int dtype, int64_t R, int N, int C, int H, int W,
 int frcnn_roi_align_bwd_kernel(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
                                int sampling_ratio, char* name, size_t len);
 
+/* Multi-scale RoIAlign over a feature pyramid (torchvision.ops.MultiScaleRoIAlign's
+ * pooling; DESIGN.md §3 "Multi-scale RoIAlign"): every RoI is pooled from the level
+ * that matches its size, one launch forward and one backward, no host sync.
+ *   n_levels L in [1, 8]; x[l] / grad_in[l] `dtype` [N,C,H[l],W[l]], fine to coarse,
+ *   all of one N, C and dtype; spatial_scales[l] fp32; rois fp32 [R,5] in image
+ *   coordinates, any order; out / grad `dtype` [R,C,PH,PW]; levels int32 [R] or NULL.
+ *   x, grad_in, H, W, spatial_scales and thresholds are HOST arrays of L (thresholds:
+ *   L - 1, may be NULL for L == 1) entries, read during the call; the pointers in x
+ *   and grad_in are device pointers.
+ * Level of a RoI, every operation fp32:
+ *   s = sqrtf((x2 - x1) * (y2 - y1))   (two subtractions, one product, a correctly
+ *   rounded root);  level = #{k : s >= thresholds[k]}.
+ * A NaN s (a NaN coordinate, a negative area) compares false everywhere: level 0.
+ * No logarithm is evaluated on the device.  The caller derives the thresholds from
+ * torchvision's LevelMapper, floor(lvl0 + log2(s / s0) + 1e-6) clamped to [k_min,
+ * k_max] minus k_min: thresholds[k - 1] is the smallest non-negative fp32 s at which
+ * that formula, in fp32 on the host, yields at least k (ops.level_thresholds).
+ * Pooling: a RoI of level l is pooled from x[l] with spatial_scales[l] exactly as
+ * frcnn_roi_align_fwd_t pools it -- the same guards (batch index, scaled coordinates
+ * beyond 2^20 under that level's scale), sampling_ratio limit, clipping of adaptive
+ * grids, separately rounded fp32 operations and one rounding of 16-bit types.  A
+ * level with H[l] == 0 or W[l] == 0 gives zeros for its RoIs.
+ *   out[n] is stored exactly once, in RoI order (no zero fill, no scatter);
+ *   levels[n], if asked for, once.
+ *   grad_in[l] sums the RoIs of level l only, in ascending RoI index and the order of
+ *   bins and samples above; every element of every level is stored exactly once,
+ *   +0 where no RoI of the level reaches (levels no RoI maps to included).  No atomics.
+ * So with idx_l the ascending indices of level l, bit for bit:
+ *   out[idx_l]  = roi_align_fwd(x[l], rois[idx_l], spatial_scales[l])
+ *   grad_in[l]  = roi_align_bwd(grad[idx_l], rois[idx_l], spatial_scales[l]).
+ * Argument errors (FRCNN_EINVAL before any HIP call): n_levels outside [1, 8], a NaN
+ * threshold or one below its predecessor (equal neighbours are accepted: a level no
+ * size reaches), and everything the single-map calls refuse, per level.  No device
+ * allocation, no synchronisation; the workspace is not touched (NULL is accepted). */
+int frcnn_roi_align_multi_fwd_t(int dtype, int n_levels, const void* const* x, const int* H, const int* W,
+                                const float* spatial_scales, const float* thresholds, const float* rois, int64_t R,
+                                int N, int C, int PH, int PW, int sampling_ratio, int aligned, void* out,
+                                int* levels, void* workspace, size_t ws_bytes, void* stream);
+int frcnn_roi_align_multi_bwd_t(int dtype, int n_levels, const void* grad, const int* H, const int* W,
+                                const float* spatial_scales, const float* thresholds, const float* rois, int64_t R,
+                                int N, int C, int PH, int PW, int sampling_ratio, int aligned, void* const* grad_in,
+                                void* workspace, size_t ws_bytes, void* stream);
+/* The kernels the two calls launch, as their template names
+ * ("roi_align_multi_fwd_kernel<ElemF32>", "roi_align_multi_bwd_tile_kernel<ElemBF16, 8>"). */
+int frcnn_roi_align_multi_fwd_kernel(int dtype, int n_levels, int64_t R, int N, int C, int PH, int PW,
+                                     int sampling_ratio, char* name, size_t len);
+int frcnn_roi_align_multi_bwd_kernel(int dtype, int n_levels, int64_t R, int N, int C, int PH, int PW,
+                                     int sampling_ratio, char* name, size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

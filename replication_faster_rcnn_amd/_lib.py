@@ -77,6 +77,10 @@ SIGNATURES = {
     "frcnn_roi_align_bwd_t": (I32, [I32, P, P, I64, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, P, SZ, P]),
     "frcnn_roi_align_fwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_roi_align_bwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_roi_align_multi_fwd_t": (I32, [I32, I32, P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, P, P, P, SZ, P]),
+    "frcnn_roi_align_multi_bwd_t": (I32, [I32, I32, P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, P, P, SZ, P]),
+    "frcnn_roi_align_multi_fwd_kernel": (I32, [I32, I32, I64, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_roi_align_multi_bwd_kernel": (I32, [I32, I32, I64, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),
@@ -316,6 +320,17 @@ def roi_align_kernel(which: str, R, N, C, H, W, PH=7, PW=7, sampling_ratio=-1, d
     fn = {"fwd": lib.frcnn_roi_align_fwd_kernel, "bwd": lib.frcnn_roi_align_bwd_kernel}[which]
     check(fn(dtype_code(dtype), int(R), int(N), int(C), int(H), int(W), int(PH), int(PW), int(sampling_ratio), buf,
              160), f"roi_align_{which}_kernel")
+    return buf.value.decode()
+
+
+def roi_align_multi_kernel(which: str, n_levels, R, N, C, PH=7, PW=7, sampling_ratio=-1, dtype=torch.float32) -> str:
+    """frcnn_roi_align_multi_fwd_kernel / _bwd_kernel (``which`` = "fwd" | "bwd"): the template
+    name of the pyramid RoIAlign kernel a call of this dtype launches.  Host only."""
+    lib = load(require_gpu=False)
+    buf = ctypes.create_string_buffer(160)
+    fn = {"fwd": lib.frcnn_roi_align_multi_fwd_kernel, "bwd": lib.frcnn_roi_align_multi_bwd_kernel}[which]
+    check(fn(dtype_code(dtype), int(n_levels), int(R), int(N), int(C), int(PH), int(PW), int(sampling_ratio), buf, 160),
+          f"roi_align_multi_{which}_kernel")
     return buf.value.decode()
 
 

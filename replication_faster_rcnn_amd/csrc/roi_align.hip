@@ -29,6 +29,12 @@
 // positive and a sample's coordinate is a nondecreasing function of its index (every
 // rounding is monotone), so the indices inside an interval are found by bisection on
 // the exact fp32 coordinate; the exact test is then applied to each sample again.
+//
+// Pyramid (DESIGN.md §3 "Multi-scale RoIAlign"): roi_align_multi_fwd_kernel and
+// roi_align_multi_bwd_tile_kernel run the same per-thread and per-wave work (align_fwd_bin,
+// align_bwd_tile) over up to 8 maps in one launch each.  A RoI's level is the number of
+// thresholds its fp32 sqrt(area) reaches; the forward takes the map of its RoI's level, the
+// backward runs over the tiles of all levels and keeps the RoIs of its tile's level.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,6 +55,7 @@ constexpr int kAlignWaves = 5;             // backward: waves (tiles) per workgr
 constexpr int kAlignStageBins = 49;        // backward: a RoI's gradients are staged in LDS up to this many bins
 constexpr int kAlignMaxDim = 1 << 24;      // H, W must be exact in fp32
 constexpr int kAlignRun = 8;               // forward: channels per thread
+constexpr int kAlignMaxLevels = 8;         // pyramid: most levels in one call
 
 struct AlignGeom {
     float sh, sw, bh, bw, count;
@@ -138,21 +145,15 @@ __device__ __forceinline__ void align_axis(float v, int size, int& lo, int& hi, 
     h = 1.f - l;
 }
 
+// The forward's work of one thread: bin (ph, pw) of RoI n for the channels [c0, c0 + kAlignRun)
+// of the map x [N,C,H,W] (the geometry is theirs in common).  Shared by the single-map and the
+// pyramid kernel, which differ only in where x, H, W and scale come from.
 template <class E>
-__global__ __launch_bounds__(256) void roi_align_fwd_kernel(const typename E::raw* __restrict__ x,
-                                                            const float* __restrict__ rois, int64_t total, int N,
-                                                            int C, int H, int W, int PH, int PW, float scale,
-                                                            int sampling_ratio, int aligned,
-                                                            typename E::raw* __restrict__ out) {
-    // one thread: one bin of one RoI for a run of kAlignRun channels (the geometry is theirs in common)
+__device__ __forceinline__ void align_fwd_bin(const typename E::raw* __restrict__ x, const float* __restrict__ rois,
+                                              int64_t n, int c0, int ph, int pw, int N, int C, int H, int W, int PH,
+                                              int PW, float scale, int sampling_ratio, int aligned,
+                                              typename E::raw* __restrict__ out) {
     constexpr int CH = kAlignRun;
-    const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int runs = (C + CH - 1) / CH;
-    const int pw = static_cast<int>(idx % PW);
-    const int ph = static_cast<int>((idx / PW) % PH);
-    const int c0 = static_cast<int>((idx / PW / PH) % runs) * CH;
-    const int64_t n = idx / PW / PH / runs;
     const int nc = C - c0 < CH ? C - c0 : CH;
     const size_t PHW = static_cast<size_t>(PH) * PW, HW = static_cast<size_t>(H) * W;
     typename E::raw* o = out + (static_cast<size_t>(n) * C + c0) * PHW + static_cast<size_t>(ph) * PW + pw;
@@ -203,6 +204,105 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(const typename E::ra
         if (j < nc) o[j * PHW] = E::narrow(acc[j] / g.count);
 }
 
+template <class E>
+__global__ __launch_bounds__(256) void roi_align_fwd_kernel(const typename E::raw* __restrict__ x,
+                                                            const float* __restrict__ rois, int64_t total, int N,
+                                                            int C, int H, int W, int PH, int PW, float scale,
+                                                            int sampling_ratio, int aligned,
+                                                            typename E::raw* __restrict__ out) {
+    // one thread: one bin of one RoI for a run of kAlignRun channels
+    constexpr int CH = kAlignRun;
+    const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int runs = (C + CH - 1) / CH;
+    const int pw = static_cast<int>(idx % PW);
+    const int ph = static_cast<int>((idx / PW) % PH);
+    const int c0 = static_cast<int>((idx / PW / PH) % runs) * CH;
+    const int64_t n = idx / PW / PH / runs;
+    align_fwd_bin<E>(x, rois, n, c0, ph, pw, N, C, H, W, PH, PW, scale, sampling_ratio, aligned, out);
+}
+
+// ------------------------------------------------- pyramid (DESIGN.md §3 "Multi-scale RoIAlign")
+// The levels of a call, by value in the kernel arguments.  Every index into the arrays is a
+// constant after unrolling, so the table stays in the argument segment (scalar loads, no scratch).
+struct AlignLevels {
+    const void* p[kAlignMaxLevels];  // forward: x_l; backward: grad_in_l
+    int H[kAlignMaxLevels], W[kAlignMaxLevels];
+    float scale[kAlignMaxLevels];
+    float thr[kAlignMaxLevels];  // thr[k - 1] = t_k for k in [1, n); ascending, none NaN
+    int n;
+};
+
+// The backward's tile space: level l owns the units [first[l], first[l + 1]).
+struct AlignTilePlan {
+    int64_t first[kAlignMaxLevels + 1];
+    int tiles_x[kAlignMaxLevels], tiles[kAlignMaxLevels];
+};
+
+// #{k : sqrt(area) >= t_k}; a NaN root (a NaN coordinate, a negative area) compares false: level 0.
+__device__ __forceinline__ int align_level(const float* __restrict__ roi, const AlignLevels& lv) {
+    const float w = roi[3] - roi[1], h = roi[4] - roi[2];
+    const float s = sqrtf(w * h);  // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt)
+    int l = 0;
+#pragma unroll
+    for (int k = 0; k < kAlignMaxLevels - 1; ++k) l += (k < lv.n - 1 && s >= lv.thr[k]) ? 1 : 0;
+    return l;
+}
+
+// A level's entry as the kernels index it: in LDS.  (Indexed by a run-time level the by-value
+// table would be copied to scratch, a chain of selects over it included: the compiler folds the
+// chain back into an indexed load.)  One thread copies it with constant indices, i.e. scalar
+// loads from the argument segment; the caller's barrier publishes it.
+struct AlignLevelView {
+    const void* p;
+    int H, W;
+    float scale;
+};
+
+__device__ __forceinline__ void align_publish(const AlignLevels& lv, AlignLevelView* tab) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kAlignMaxLevels; ++k) tab[k] = AlignLevelView{lv.p[k], lv.H[k], lv.W[k], lv.scale[k]};
+    }
+}
+
+// Entry l of the published table for a wave-uniform l, in scalar registers.
+__device__ __forceinline__ AlignLevelView align_view_uniform(const AlignLevelView* tab, int l) {
+    const AlignLevelView t = tab[l];
+    const uint64_t p = reinterpret_cast<uint64_t>(t.p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(p));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(p >> 32));
+    return AlignLevelView{reinterpret_cast<const void*>((static_cast<uint64_t>(hi) << 32) | lo),
+                          __builtin_amdgcn_readfirstlane(t.H), __builtin_amdgcn_readfirstlane(t.W),
+                          __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.scale)))};
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void roi_align_multi_fwd_kernel(AlignLevels lv, const float* __restrict__ rois,
+                                                                  int64_t total, int N, int C, int runs, int PH,
+                                                                  int PW, int sampling_ratio, int aligned,
+                                                                  typename E::raw* __restrict__ out,
+                                                                  int* __restrict__ levels) {
+    // roi_align_fwd_kernel's thread mapping; each thread pools from the map of its RoI's level
+    constexpr int CH = kAlignRun;
+    __shared__ AlignLevelView tab[kAlignMaxLevels];
+    align_publish(lv, tab);
+    __syncthreads();
+    const int64_t idx = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int pw = static_cast<int>(idx % PW);
+    const int ph = static_cast<int>((idx / PW) % PH);
+    const int c0 = static_cast<int>((idx / PW / PH) % runs) * CH;  // runs >= 1 also for C == 0 (levels only)
+    const int64_t n = idx / PW / PH / runs;
+    const int l = align_level(rois + n * 5, lv);
+    if (levels && c0 == 0 && ph == 0 && pw == 0) levels[n] = l;
+    const AlignLevelView v = tab[l];  // l < lv.n <= kAlignMaxLevels
+    // a level without pixels guards all its RoIs: zeros, nothing read
+    const int n_img = v.H > 0 && v.W > 0 ? N : 0;
+    align_fwd_bin<E>(static_cast<const typename E::raw*>(v.p), rois, n, c0, ph, pw, n_img, C, v.H, v.W, PH, PW,
+                     v.scale, sampling_ratio, aligned, out);
+}
+
 // The four additions of one sample into the tile (al / ah: the rows of yl / yh at this
 // lane's channel; ol / oh: the offsets of xl / xh), in the contract's order.
 __device__ __forceinline__ void align_add4(float* al, float* ah, int ol, int oh, bool in_yl, bool in_yh, bool in_xl,
@@ -239,16 +339,27 @@ __device__ __forceinline__ uint64_t align_bits(uint64_t m, int first, int n) {
     return n >= 64 ? s : s & ((1ull << n) - 1ull);
 }
 
-template <class E, int T>
-__global__ __launch_bounds__(64 * kAlignWaves) void roi_align_bwd_tile_kernel(
-    const typename E::raw* __restrict__ grad, const float* __restrict__ rois, int R, int N, int C, int H, int W, int PH,
-    int PW, float scale, int sampling_ratio, int aligned, int tiles_x, int tiles, int cgroups, int64_t units,
-    typename E::raw* __restrict__ grad_in) {
+// Which RoIs a backward wave sums: all of its image (one map), or those of its level too (pyramid).
+struct AlignKeepAll {
+    __device__ __forceinline__ bool operator()(const float*) const { return true; }
+};
+struct AlignKeepLevel {
+    const AlignLevels& lv;
+    int level;
+    __device__ __forceinline__ bool operator()(const float* roi) const { return align_level(roi, lv) == level; }
+};
+
+// The backward's work of one wave: tile `unit` of the map [N,C,H,W] behind grad_in (`live`: the unit
+// exists; a wave without one only joins the barrier).  Shared by the single-map and the pyramid kernel.
+template <class E, int T, class Keep>
+__device__ __forceinline__ void align_bwd_tile(const typename E::raw* __restrict__ grad,
+                                               const float* __restrict__ rois, int R, int N, int C, int H, int W,
+                                               int PH, int PW, float scale, int sampling_ratio, int aligned,
+                                               int tiles_x, int tiles, int cgroups, int64_t unit, bool live,
+                                               typename E::raw* __restrict__ grad_in, Keep keep) {
     static_assert(T * T == 64, "the write-out maps one lane to one pixel of the tile");
     extern __shared__ __attribute__((aligned(16))) float align_lds[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int64_t unit = static_cast<int64_t>(blockIdx.x) * kAlignWaves + wid;
-    const bool live = unit < units;  // whole wave
     constexpr int kWaveWords = T * T * kAlignTileStride + 64 * kAlignStageBins;
     float* acc = align_lds + wid * kWaveWords;
     float* stage = acc + T * T * kAlignTileStride;  // [channel][bin], an odd stride: conflict-free either way
@@ -278,7 +389,7 @@ __global__ __launch_bounds__(64 * kAlignWaves) void roi_align_bwd_tile_kernel(
             if (r < R) {
                 const AlignGeom gl = align_geom(rois + static_cast<size_t>(r) * 5, N, PH, PW, scale, sampling_ratio,
                                                 aligned != 0);
-                mine = gl.ok && gl.b == b;
+                mine = gl.ok && gl.b == b && keep(rois + static_cast<size_t>(r) * 5);
             }
             uint64_t mask = __ballot(mine);
             while (mask) {
@@ -435,6 +546,48 @@ __global__ __launch_bounds__(64 * kAlignWaves) void roi_align_bwd_tile_kernel(
     }
 }
 
+template <class E, int T>
+__global__ __launch_bounds__(64 * kAlignWaves) void roi_align_bwd_tile_kernel(
+    const typename E::raw* __restrict__ grad, const float* __restrict__ rois, int R, int N, int C, int H, int W, int PH,
+    int PW, float scale, int sampling_ratio, int aligned, int tiles_x, int tiles, int cgroups, int64_t units,
+    typename E::raw* __restrict__ grad_in) {
+    const int64_t unit = static_cast<int64_t>(blockIdx.x) * kAlignWaves + (threadIdx.x >> 6);
+    align_bwd_tile<E, T>(grad, rois, R, N, C, H, W, PH, PW, scale, sampling_ratio, aligned, tiles_x, tiles, cgroups,
+                         unit, unit < units, grad_in, AlignKeepAll{});
+}
+
+// One launch over the tiles of every level, level after level: a wave finds its level from the
+// prefix table, then runs the single-map walk on that level's geometry and RoIs.  A workgroup's
+// waves may belong to different levels; each has its own LDS and they meet only at the barrier.
+template <class E, int T>
+__global__ __launch_bounds__(64 * kAlignWaves) void roi_align_multi_bwd_tile_kernel(
+    const typename E::raw* __restrict__ grad, const float* __restrict__ rois, int R, int N, int C, int PH, int PW,
+    int sampling_ratio, int aligned, int cgroups, int64_t units, AlignLevels lv, AlignTilePlan plan) {
+    __shared__ AlignLevelView tab[kAlignMaxLevels];
+    __shared__ int64_t tab_first[kAlignMaxLevels];
+    __shared__ int tab_tiles_x[kAlignMaxLevels], tab_tiles[kAlignMaxLevels];
+    align_publish(lv, tab);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kAlignMaxLevels; ++k)
+            tab_first[k] = plan.first[k], tab_tiles_x[k] = plan.tiles_x[k], tab_tiles[k] = plan.tiles[k];
+    }
+    __syncthreads();
+    const int64_t unit = static_cast<int64_t>(blockIdx.x) * kAlignWaves + (threadIdx.x >> 6);
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < kAlignMaxLevels; ++k) l += (k < lv.n && unit >= plan.first[k]) ? 1 : 0;
+    l = __builtin_amdgcn_readfirstlane(l);  // the same in every lane of the wave; l < lv.n <= kAlignMaxLevels
+    const AlignLevelView v = align_view_uniform(tab, l);
+    const int64_t first = tab_first[l];
+    const int tiles_x = __builtin_amdgcn_readfirstlane(tab_tiles_x[l]);
+    const int tiles = __builtin_amdgcn_readfirstlane(tab_tiles[l]);
+    // a unit past the last one lands on the last level with tiles to spare; it is not live
+    align_bwd_tile<E, T>(grad, rois, R, N, C, v.H, v.W, PH, PW, v.scale, sampling_ratio, aligned, tiles_x, tiles,
+                         cgroups, unit - first, unit < units,
+                         static_cast<typename E::raw*>(const_cast<void*>(v.p)), AlignKeepLevel{lv, l});
+}
+
 const char* align_elem_name(int dtype) {
     return dtype == FRCNN_F16 ? "ElemF16" : dtype == FRCNN_BF16 ? "ElemBF16" : "ElemF32";
 }
@@ -480,6 +633,78 @@ int align_bwd_launch(const void* grad, const float* rois, int R, int N, int C, i
                        lds, st, static_cast<const raw*>(grad), rois, R, N, C, H, W, PH, PW, scale, sampling_ratio,
                        aligned, tiles_x, static_cast<int>(tiles), cgroups, units, static_cast<raw*>(grad_in));
     return check_launch("roi_align_bwd_tile_kernel");
+}
+
+// The pyramid calls' argument checks and level table, before any HIP call.  `p` may be null
+// (the name queries); a level's pointer is needed only where the level has elements.
+int align_levels(const char* fn, int dtype, int n_levels, const void* const* p, const int* H, const int* W,
+                 const float* scales, const float* thresholds, int64_t R, int N, int C, int PH, int PW,
+                 int sampling_ratio, AlignLevels& lv) {
+    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= kAlignMaxLevels, "%s: n_levels %d is not in [1, %d]", fn, n_levels,
+                  kAlignMaxLevels);
+    FRCNN_REQUIRE(H && W && scales, "%s: null %s", fn, !H ? "H" : !W ? "W" : "spatial_scales");
+    FRCNN_REQUIRE(n_levels == 1 || thresholds, "%s: null thresholds", fn);
+    std::memset(&lv, 0, sizeof(lv));
+    lv.n = n_levels;
+    for (int l = 0; l < n_levels; ++l) {
+        if (int rc = align_check(fn, dtype, R, N, C, H[l], W[l], PH, PW, sampling_ratio)) return rc;
+        lv.p[l] = p ? p[l] : nullptr;
+        lv.H[l] = H[l];
+        lv.W[l] = W[l];
+        lv.scale[l] = scales[l];
+    }
+    for (int k = 0; k + 1 < n_levels; ++k) {
+        const float t = thresholds[k];
+        FRCNN_REQUIRE(t == t, "%s: thresholds[%d] is NaN", fn, k);
+        FRCNN_REQUIRE(k == 0 || t >= thresholds[k - 1], "%s: thresholds[%d] = %g is below thresholds[%d] = %g", fn, k,
+                      static_cast<double>(t), k - 1, static_cast<double>(thresholds[k - 1]));
+        lv.thr[k] = t;
+    }
+    return FRCNN_OK;
+}
+
+template <class E>
+int align_multi_fwd_launch(const AlignLevels& lv, const float* rois, int64_t R, int N, int C, int PH, int PW,
+                           int sampling_ratio, int aligned, void* out, int* levels, hipStream_t st) {
+    using raw = typename E::raw;
+    const int runs = C > 0 ? (C + kAlignRun - 1) / kAlignRun : 1;  // C == 0: one thread row, for `levels`
+    const int64_t total = R * runs * PH * PW;                      // threads
+    const unsigned grid = static_cast<unsigned>((total + 255) / 256);
+    hipLaunchKernelGGL(roi_align_multi_fwd_kernel<E>, dim3(grid), dim3(256), 0, st, lv, rois, total, N, C, runs, PH,
+                       PW, sampling_ratio, aligned, static_cast<raw*>(out), levels);
+    return check_launch("roi_align_multi_fwd_kernel");
+}
+
+template <class E>
+int align_multi_bwd_launch(const AlignLevels& lv, const void* grad, const float* rois, int R, int N, int C, int PH,
+                           int PW, int sampling_ratio, int aligned, hipStream_t st) {
+    using raw = typename E::raw;
+    constexpr int T = kAlignTile;
+    const int cgroups = (C + 63) / 64;
+    AlignTilePlan plan;
+    std::memset(&plan, 0, sizeof(plan));
+    int64_t units = 0;
+    for (int l = 0; l < kAlignMaxLevels; ++l) {
+        plan.first[l] = units;
+        if (l >= lv.n) continue;
+        const int tiles_x = (lv.W[l] + T - 1) / T, tiles_y = (lv.H[l] + T - 1) / T;
+        const int64_t tiles = static_cast<int64_t>(tiles_x) * tiles_y;
+        FRCNN_REQUIRE(tiles <= 0x7fffffff, "frcnn_roi_align_multi_bwd_t: level %d too large (%lld tiles)", l,
+                      static_cast<long long>(tiles));
+        plan.tiles_x[l] = tiles_x;
+        plan.tiles[l] = static_cast<int>(tiles);
+        units += tiles * cgroups * N;
+    }
+    plan.first[kAlignMaxLevels] = units;
+    if (units == 0) return FRCNN_OK;
+    const int64_t blocks = (units + kAlignWaves - 1) / kAlignWaves;
+    FRCNN_REQUIRE(blocks <= 0x7fffffff, "frcnn_roi_align_multi_bwd_t: maps too large (%lld tiles)",
+                  static_cast<long long>(units));
+    const size_t lds = sizeof(float) * kAlignWaves * (T * T * kAlignTileStride + 64 * kAlignStageBins);
+    hipLaunchKernelGGL((roi_align_multi_bwd_tile_kernel<E, T>), dim3(static_cast<unsigned>(blocks)),
+                       dim3(64 * kAlignWaves), lds, st, static_cast<const raw*>(grad), rois, R, N, C, PH, PW,
+                       sampling_ratio, aligned, cgroups, units, lv, plan);
+    return check_launch("roi_align_multi_bwd_tile_kernel");
 }
 
 }  // namespace
@@ -565,6 +790,83 @@ extern "C" int frcnn_roi_align_bwd_kernel(int dtype, int64_t R, int N, int C, in
     if (int rc = align_check(fn, dtype, R, N, C, H, W, PH, PW, sampling_ratio)) return rc;
     FRCNN_REQUIRE(name && len > 0, "%s: null name", fn);
     const int n = snprintf(name, len, "roi_align_bwd_tile_kernel<%s, %d>", align_elem_name(dtype), kAlignTile);
+    FRCNN_REQUIRE(n >= 0 && static_cast<size_t>(n) < len, "%s: name buffer of %zu bytes too small", fn, len);
+    return FRCNN_OK;
+}
+
+// ------------------------------------------------------------------ pyramid
+extern "C" int frcnn_roi_align_multi_fwd_t(int dtype, int n_levels, const void* const* x, const int* H, const int* W,
+                                           const float* spatial_scales, const float* thresholds, const float* rois,
+                                           int64_t R, int N, int C, int PH, int PW, int sampling_ratio, int aligned,
+                                           void* out, int* levels, void* workspace, size_t ws_bytes, void* stream) {
+    (void)workspace;
+    (void)ws_bytes;
+    const char* fn = "frcnn_roi_align_multi_fwd_t";
+    AlignLevels lv;
+    FRCNN_REQUIRE(n_levels < 1 || n_levels > kAlignMaxLevels || x, "%s: null x", fn);
+    if (int rc = align_levels(fn, dtype, n_levels, x, H, W, spatial_scales, thresholds, R, N, C, PH, PW,
+                              sampling_ratio, lv))
+        return rc;
+    const int64_t per_roi = static_cast<int64_t>(C) * PH * PW;
+    FRCNN_REQUIRE(R <= (int64_t{1} << 38) / (per_roi > 0 ? per_roi : int64_t{PH} * PW), "%s: output too large", fn);
+    if (R == 0 || (per_roi == 0 && !levels)) return FRCNN_OK;
+    FRCNN_REQUIRE(rois, "%s: null rois", fn);
+    FRCNN_REQUIRE(out || per_roi == 0, "%s: null out", fn);
+    for (int l = 0; l < n_levels; ++l)
+        FRCNN_REQUIRE(lv.p[l] || N == 0 || C == 0 || lv.H[l] == 0 || lv.W[l] == 0, "%s: null x[%d]", fn, l);
+    hipStream_t st = as_stream(stream);
+    if (dtype == FRCNN_F16)
+        return align_multi_fwd_launch<ElemF16>(lv, rois, R, N, C, PH, PW, sampling_ratio, aligned, out, levels, st);
+    if (dtype == FRCNN_BF16)
+        return align_multi_fwd_launch<ElemBF16>(lv, rois, R, N, C, PH, PW, sampling_ratio, aligned, out, levels, st);
+    return align_multi_fwd_launch<ElemF32>(lv, rois, R, N, C, PH, PW, sampling_ratio, aligned, out, levels, st);
+}
+
+extern "C" int frcnn_roi_align_multi_bwd_t(int dtype, int n_levels, const void* grad, const int* H, const int* W,
+                                           const float* spatial_scales, const float* thresholds, const float* rois,
+                                           int64_t R, int N, int C, int PH, int PW, int sampling_ratio, int aligned,
+                                           void* const* grad_in, void* workspace, size_t ws_bytes, void* stream) {
+    (void)workspace;
+    (void)ws_bytes;
+    const char* fn = "frcnn_roi_align_multi_bwd_t";
+    AlignLevels lv;
+    FRCNN_REQUIRE(n_levels < 1 || n_levels > kAlignMaxLevels || grad_in, "%s: null grad_in", fn);
+    if (int rc = align_levels(fn, dtype, n_levels, grad_in, H, W, spatial_scales, thresholds, R, N, C, PH, PW,
+                              sampling_ratio, lv))
+        return rc;
+    if (N == 0 || C == 0) return FRCNN_OK;
+    for (int l = 0; l < n_levels; ++l)
+        FRCNN_REQUIRE(lv.p[l] || lv.H[l] == 0 || lv.W[l] == 0, "%s: null grad_in[%d]", fn, l);
+    FRCNN_REQUIRE(R == 0 || (grad && rois), "%s: null %s", fn, grad ? "rois" : "grad");
+    hipStream_t st = as_stream(stream);
+    const int r = static_cast<int>(R);
+    if (dtype == FRCNN_F16)
+        return align_multi_bwd_launch<ElemF16>(lv, grad, rois, r, N, C, PH, PW, sampling_ratio, aligned, st);
+    if (dtype == FRCNN_BF16)
+        return align_multi_bwd_launch<ElemBF16>(lv, grad, rois, r, N, C, PH, PW, sampling_ratio, aligned, st);
+    return align_multi_bwd_launch<ElemF32>(lv, grad, rois, r, N, C, PH, PW, sampling_ratio, aligned, st);
+}
+
+extern "C" int frcnn_roi_align_multi_fwd_kernel(int dtype, int n_levels, int64_t R, int N, int C, int PH, int PW,
+                                                int sampling_ratio, char* name, size_t len) {
+    const char* fn = "frcnn_roi_align_multi_fwd_kernel";
+    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= kAlignMaxLevels, "%s: n_levels %d is not in [1, %d]", fn, n_levels,
+                  kAlignMaxLevels);
+    if (int rc = align_check(fn, dtype, R, N, C, 0, 0, PH, PW, sampling_ratio)) return rc;
+    FRCNN_REQUIRE(name && len > 0, "%s: null name", fn);
+    const int n = snprintf(name, len, "roi_align_multi_fwd_kernel<%s>", align_elem_name(dtype));
+    FRCNN_REQUIRE(n >= 0 && static_cast<size_t>(n) < len, "%s: name buffer of %zu bytes too small", fn, len);
+    return FRCNN_OK;
+}
+
+extern "C" int frcnn_roi_align_multi_bwd_kernel(int dtype, int n_levels, int64_t R, int N, int C, int PH, int PW,
+                                                int sampling_ratio, char* name, size_t len) {
+    const char* fn = "frcnn_roi_align_multi_bwd_kernel";
+    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= kAlignMaxLevels, "%s: n_levels %d is not in [1, %d]", fn, n_levels,
+                  kAlignMaxLevels);
+    if (int rc = align_check(fn, dtype, R, N, C, 0, 0, PH, PW, sampling_ratio)) return rc;
+    FRCNN_REQUIRE(name && len > 0, "%s: null name", fn);
+    const int n = snprintf(name, len, "roi_align_multi_bwd_tile_kernel<%s, %d>", align_elem_name(dtype), kAlignTile);
     FRCNN_REQUIRE(n >= 0 && static_cast<size_t>(n) < len, "%s: name buffer of %zu bytes too small", fn, len);
     return FRCNN_OK;
 }

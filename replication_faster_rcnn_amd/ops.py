@@ -11,6 +11,11 @@
   order of torchvision's CPU kernel, forward and a deterministic backward (no
   reference counterpart: the RoI feature extractor users swap in for
   ``roi_pool``; DESIGN.md §3 "RoIAlign").
+* ``multiscale_roi_align(features, boxes, output_size, spatial_scales,
+  sampling_ratio)`` / ``MultiScaleRoIAlign`` -- ``torchvision.ops.
+  MultiScaleRoIAlign``'s pooling over a feature pyramid, the level of every RoI
+  decided inside one forward and one backward launch (DESIGN.md §3 "Multi-scale
+  RoIAlign"); ``roi_align``'s input rule.
 * ``propose(...)`` -- the batched proposal layer (nets/rpn.py:47-79 over all
   images at once, replacing the per-image loop nets/rpn.py:131-136).
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
@@ -33,7 +38,7 @@
 Two input rules (tests/test_gpu_wrapper_inputs.py):
 
 * The reference-signature drop-ins (``nms``, ``roi_pool*``, ``roi_pool_head``,
-  ``roi_align``, ``rpn_head_epilogue``) convert whatever they are given: inputs
+  ``roi_align``, ``multiscale_roi_align``, ``rpn_head_epilogue``) convert whatever they are given: inputs
   may live on the CPU (reference style), be strided views or another float type;
   they are moved to the current HIP device as contiguous fp32, and results are
   returned on the input's device.  They raise only on shapes that do not belong
@@ -383,6 +388,224 @@ def roi_align(input: torch.Tensor, boxes, output_size, spatial_scale: float = 1.
     out = _RoIAlignFunction.apply(x, rois, int(ph), int(pw), float(spatial_scale), int(sampling_ratio),
                                   bool(aligned))
     return out.to(out_dev)
+
+
+# ------------------------------------------------------ multi-scale roi_align
+ROI_ALIGN_MAX_LEVELS = 8
+_level_cache = {}     # (k_min, k_max, s0, lvl0) -> thresholds
+_pyramid_cache = {}   # (scales, s0, lvl0) -> (k_min, k_max, thresholds)
+
+
+def level_formula(s: torch.Tensor, k_min: int, k_max: int, canonical_scale=224, canonical_level=4) -> torch.Tensor:
+    """torchvision's ``LevelMapper`` on ``s = sqrt(area)``, a CPU fp32 tensor: int64 levels
+    counted from 0 (``floor(lvl0 + log2(s / s0) + 1e-6)`` clamped to [k_min, k_max], minus k_min)."""
+    lvl = torch.floor(canonical_level + torch.log2(s / canonical_scale) + torch.tensor(1e-6, dtype=s.dtype))
+    return torch.clamp(lvl, min=k_min, max=k_max).to(torch.int64) - k_min
+
+
+def level_thresholds(k_min: int, k_max: int, canonical_scale=224, canonical_level=4) -> Tuple[float, ...]:
+    """The ``k_max - k_min`` ascending fp32 thresholds the kernels count against
+    (``level = #{k : sqrt(area) >= t_k}``): ``t_k`` is the smallest non-negative fp32 value at
+    which ``level_formula`` yields at least ``k``, found by bisection over the fp32 bit
+    patterns from +0 to +inf (the formula is nondecreasing).  Host only; cached."""
+    key = (int(k_min), int(k_max), canonical_scale, canonical_level)
+    thr = _level_cache.get(key)
+    if thr is None:
+        n = key[1] - key[0]
+        if n < 0:
+            raise RuntimeError(f"level_thresholds: k_max {k_max} is below k_min {k_min}")
+        want = torch.arange(1, n + 1, dtype=torch.int64)
+        lo = torch.zeros(n, dtype=torch.int32)                    # +0: level 0, below every k
+        hi = torch.full((n,), 0x7F800000, dtype=torch.int32)      # +inf: level k_max - k_min
+        while bool((hi - lo > 1).any()):
+            mid = lo + (hi - lo) // 2
+            ge = level_formula(mid.view(torch.float32), key[0], key[1], canonical_scale, canonical_level) >= want
+            hi = torch.where(ge, mid, hi)
+            lo = torch.where(ge, lo, mid)
+        thr = tuple(float(v) for v in hi.view(torch.float32))
+        _level_cache[key] = thr
+    return thr
+
+
+def _pyramid_levels(scales, canonical_scale, canonical_level):
+    """(k_min, k_max, thresholds) of a pyramid's scales, as torchvision's ``_setup_scales``
+    derives the level range: -log2 of the first and of the last scale, in fp32, truncated."""
+    key = (tuple(scales), canonical_scale, canonical_level)
+    hit = _pyramid_cache.get(key)
+    if hit is None:
+        if any(not s > 0 for s in key[0]):
+            raise RuntimeError(f"multiscale_roi_align: spatial_scales must be positive; got {list(scales)}")
+        k_min = int(-torch.log2(torch.tensor(key[0][0], dtype=torch.float32)).item())
+        k_max = int(-torch.log2(torch.tensor(key[0][-1], dtype=torch.float32)).item())
+        if len(key[0]) != k_max - k_min + 1:
+            raise RuntimeError(f"multiscale_roi_align: {len(key[0])} feature maps, but scales {list(scales)} span "
+                               f"the levels {k_min}..{k_max} ({k_max - k_min + 1} maps, one per octave)")
+        hit = (k_min, k_max, level_thresholds(k_min, k_max, canonical_scale, canonical_level))
+        _pyramid_cache[key] = hit
+    return hit
+
+
+class _PyramidArgs:
+    """The per-level host arrays of the C-ABI pair for one call."""
+
+    def __init__(self, shapes, scales, thresholds):
+        L = len(shapes)
+        self.L = L
+        self.H = (_lib.I32 * L)(*[s[2] for s in shapes])
+        self.W = (_lib.I32 * L)(*[s[3] for s in shapes])
+        self.scales = (_lib.F32 * L)(*scales)
+        self.thr = (_lib.F32 * max(L - 1, 1))(*thresholds)
+
+    @staticmethod
+    def ptrs(tensors):
+        return (_lib.P * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _multiscale_fwd(xs, rois, ph, pw, scales, thresholds, sr, aligned, want_levels):
+    lib = _lib.load()
+    x0 = xs[0]
+    N, C = x0.shape[:2]
+    R = rois.size(0)
+    code = _POOL_DTYPE_CODE.get(x0.dtype)
+    if code is None:
+        raise _pool_dtype_error("multiscale_roi_align forward", x0.dtype)
+    a = _PyramidArgs([x.shape for x in xs], scales, thresholds)
+    out = torch.empty((R, C, ph, pw), dtype=x0.dtype, device=x0.device)
+    levels = torch.empty((R,), dtype=torch.int32, device=x0.device) if want_levels else None
+    _lib.check(lib.frcnn_roi_align_multi_fwd_t(code, a.L, a.ptrs(xs), a.H, a.W, a.scales, a.thr, _lib.ptr(rois), R, N,
+                                               C, ph, pw, int(sr), int(bool(aligned)), _lib.ptr(out),
+                                               _lib.ptr(levels), None, 0, _lib.stream_ptr()),
+               "multiscale_roi_align forward")
+    return out, levels
+
+
+def _multiscale_bwd(grad, rois, shapes, scales, thresholds, sr, aligned):
+    lib = _lib.load()
+    N, C = shapes[0][:2]
+    R, _, ph, pw = grad.shape
+    code = _POOL_DTYPE_CODE.get(grad.dtype)
+    if code is None:
+        raise _pool_dtype_error("multiscale_roi_align backward", grad.dtype)
+    a = _PyramidArgs(shapes, scales, thresholds)
+    gis = [torch.empty(tuple(s), dtype=grad.dtype, device=grad.device) for s in shapes]
+    _lib.check(lib.frcnn_roi_align_multi_bwd_t(code, a.L, _lib.ptr(grad), a.H, a.W, a.scales, a.thr, _lib.ptr(rois), R,
+                                               N, C, ph, pw, int(sr), int(bool(aligned)), a.ptrs(gis), None, 0,
+                                               _lib.stream_ptr()),
+               "multiscale_roi_align backward")
+    return gis
+
+
+class _MultiScaleRoIAlignFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rois, ph, pw, scales, thresholds, sr, aligned, want_levels, *xs):
+        out, levels = _multiscale_fwd(xs, rois, ph, pw, scales, thresholds, sr, aligned, want_levels)
+        ctx.save_for_backward(rois)
+        ctx.meta = ([tuple(x.shape) for x in xs], scales, thresholds, sr, aligned, xs[0].dtype)
+        if levels is None:
+            return out
+        ctx.mark_non_differentiable(levels)
+        return out, levels
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, *_):
+        (rois,) = ctx.saved_tensors
+        shapes, scales, thresholds, sr, aligned, dtype = ctx.meta
+        gis = _multiscale_bwd(_pool_grad(grad_out, dtype), rois, shapes, scales, thresholds, sr, aligned)
+        return (None,) * 8 + tuple(gis)   # a gradient for every level: zeros where no RoI mapped
+
+
+def multiscale_roi_align(features, boxes, output_size, spatial_scales, sampling_ratio: int, *, canonical_scale=224,
+                         canonical_level=4, aligned: bool = False, return_levels: bool = False):
+    """``torchvision.ops.MultiScaleRoIAlign``'s pooling over a feature pyramid in one launch,
+    forward and backward (frcnn_roi_align_multi_fwd_t / _bwd_t; DESIGN.md §3 "Multi-scale
+    RoIAlign" is the contract).  ``features``: the maps [N, C, H_l, W_l], fine to coarse,
+    of one N, C and dtype, at most 8; ``spatial_scales``: one per map, an octave apart
+    (``k_min`` / ``k_max`` are -log2 of the first / last, as torchvision derives them);
+    ``boxes``: [K, 5] (batch_idx, x1, y1, x2, y2) in image coordinates or a list of [L_i, 4]
+    tensors, in any order.  Each RoI is pooled from the level torchvision's ``LevelMapper``
+    gives it -- decided on the device, with no host sync -- exactly as ``roi_align`` pools
+    it from that map alone; the output comes in RoI order, and the backward returns a
+    deterministic gradient for every level (zeros for a level no RoI mapped to).
+    ``return_levels``: also return the int32 [K] level of each RoI.
+
+    ``roi_align``'s input rule: host, strided or other float inputs are converted, results
+    come back on the first map's device, float16 / bfloat16 maps are never widened.  One map
+    delegates to ``roi_align``."""
+    op = "multiscale_roi_align"
+    feats = list(features)
+    if not feats or any(not isinstance(f, torch.Tensor) or f.dim() != 4 for f in feats):
+        raise RuntimeError(f"{op}: features must be a non-empty sequence of [N, C, H, W] tensors")
+    if len(feats) > ROI_ALIGN_MAX_LEVELS:
+        raise RuntimeError(f"{op}: at most {ROI_ALIGN_MAX_LEVELS} levels; got {len(feats)}")
+    f0 = feats[0]
+    for i, f in enumerate(feats):
+        if f.shape[:2] != f0.shape[:2] or f.dtype != f0.dtype:
+            raise RuntimeError(f"{op}: the levels share N, C and dtype; features[{i}] is {f.dtype} "
+                               f"{list(f.shape)}, features[0] is {f0.dtype} {list(f0.shape)}")
+    scales = tuple(float(s) for s in spatial_scales)
+    if len(scales) != len(feats):
+        raise RuntimeError(f"{op}: {len(feats)} feature maps but {len(scales)} spatial_scales")
+    _, _, thresholds = _pyramid_levels(scales, canonical_scale, canonical_level)
+    try:
+        ph, pw = (output_size, output_size) if isinstance(output_size, int) else (int(v) for v in output_size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{op}: output_size must be an int or (h, w); got {output_size!r}") from None
+    if isinstance(boxes, (list, tuple)):
+        if len(boxes) != f0.size(0):
+            raise RuntimeError(f"{op}: a list of boxes needs one entry per image; got {len(boxes)} for "
+                               f"{f0.size(0)} images")
+        if any(not isinstance(b, torch.Tensor) or b.dim() != 2 or b.size(1) != 4 for b in boxes):
+            raise RuntimeError(f"{op}: every entry of a list of boxes must be a [L, 4] tensor")
+    if len(feats) == 1:
+        out = roi_align(f0, boxes, (ph, pw), scales[0], sampling_ratio, aligned)
+        return (out, torch.zeros(out.size(0), dtype=torch.int32, device=out.device)) if return_levels else out
+    out_dev = f0.device
+    xs = [_pool_input(f) for f in feats]  # differentiable moves, so CPU leaf tensors get their grad
+    rois = _to_dev(_boxes_to_rois(boxes))
+    res = _MultiScaleRoIAlignFunction.apply(rois, int(ph), int(pw), scales, thresholds, int(sampling_ratio),
+                                            bool(aligned), bool(return_levels), *xs)
+    if return_levels:
+        return res[0].to(out_dev), res[1].to(out_dev)
+    return res.to(out_dev)
+
+
+class MultiScaleRoIAlign(torch.nn.Module):
+    """``torchvision.ops.MultiScaleRoIAlign`` on ``multiscale_roi_align``: ``forward(x, boxes,
+    image_shapes)`` takes the dict of feature maps (those named in ``featmap_names`` are
+    used, in the dict's order, fine to coarse), a list of [L_i, 4] boxes per image and the
+    list of the images' (h, w), and returns [sum L_i, C, *output_size].  The scales are
+    inferred as torchvision infers them (2 ** round(log2(map size / largest image size)) per
+    axis, the two axes agreeing) on the first call and cached with the level thresholds."""
+
+    def __init__(self, featmap_names, output_size, sampling_ratio: int, *, canonical_scale=224, canonical_level=4):
+        super().__init__()
+        self.featmap_names = list(featmap_names)
+        self.output_size = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
+        self.sampling_ratio = int(sampling_ratio)
+        self.canonical_scale, self.canonical_level = canonical_scale, canonical_level
+        self.scales = None
+
+    @staticmethod
+    def infer_scales(features, image_shapes):
+        max_h, max_w = max(int(s[0]) for s in image_shapes), max(int(s[1]) for s in image_shapes)
+        scales = []
+        for f in features:
+            per_axis = [2.0 ** float(torch.tensor(float(s) / float(o)).log2().round())
+                        for s, o in zip(f.shape[-2:], (max_h, max_w))]
+            if per_axis[0] != per_axis[1]:
+                raise RuntimeError(f"MultiScaleRoIAlign: a {list(f.shape[-2:])} map of {max_h} x {max_w} images "
+                                   f"has the scales {per_axis[0]} and {per_axis[1]} along its two axes")
+            scales.append(per_axis[0])
+        return tuple(scales)
+
+    def forward(self, x, boxes, image_shapes):
+        feats = [v for k, v in x.items() if k in self.featmap_names]
+        if self.scales is None:
+            self.scales = self.infer_scales(feats, image_shapes)
+            _pyramid_levels(self.scales, self.canonical_scale, self.canonical_level)
+        return multiscale_roi_align(feats, list(boxes), self.output_size, self.scales, self.sampling_ratio,
+                                    canonical_scale=self.canonical_scale, canonical_level=self.canonical_level)
 
 
 # ------------------------------------------------------------------ proposals
