@@ -349,6 +349,54 @@ int frcnn_roi_align_multi_fwd_kernel(int dtype, int n_levels, int64_t R, int N, 
 int frcnn_roi_align_multi_bwd_kernel(int dtype, int n_levels, int64_t R, int N, int C, int PH, int PW,
                                      int sampling_ratio, char* name, size_t len);
 
+/* FPN proposal layer: torchvision's RegionProposalNetwork.filter_proposals with
+ * BoxCoder(weights=(1, 1, 1, 1)) over a feature pyramid (DESIGN.md §3 "FPN proposals"):
+ * per-level top-k, decode, clip, filters, level-wise NMS and the merge, four launches,
+ * no host sync, no device allocation.
+ *   n_levels L in [1, 8]; objectness[l] `dtype` [N,K,H[l],W[l]]; deltas[l] `dtype`
+ *   [N,4K,H[l],W[l]], channel 4k + c -- the RPN head's conv outputs, contiguous, read in
+ *   place (no permute, no cast; a 16-bit value is widened exactly at the load, so every
+ *   output is bit-identical to the call on the fp32 copies); anchor_bases[l] fp32 [K,4]
+ *   (x1, y1, x2, y2), 16-byte aligned; image_sizes fp32 [N,2] of (h, w), a device pointer.
+ *   objectness, deltas, anchor_bases, H, W, stride_h and stride_w are HOST arrays of L
+ *   entries, read during the call; the pointers in the first three are device pointers.
+ * Per image and level, A = K*H*W anchors, anchor a = (y*W + x)*K + k = base[k] + (x*stride_w,
+ * y*stride_h, x*stride_w, y*stride_h), one fp32 addition per coordinate, formed in registers:
+ *   1. selection: the first min(pre_nms, A) anchors in the stable descending order of the
+ *      raw logit -- every NaN first, -0.0 == +0.0, ties by ascending a -- before any filter;
+ *   2. decode of those, fp32, every operation rounded separately: w = x2 - x1, cx = x1 + 0.5*w;
+ *      dw, dh clamped from above at float(log(1000/16)) (a NaN stays); pcx = dx*w + cx;
+ *      pw = exp(dw)*w with a correctly rounded exp; box = pcx -+ 0.5*pw (the same in y);
+ *   3. clip x to [0, w_n], y to [0, h_n] (a NaN stays); keep a box iff x2 - x1 >= min_size and
+ *      y2 - y1 >= min_size and logit >= logit_thresh (a NaN fails each; -inf keeps every
+ *      non-NaN logit).  logit_thresh is the caller's score threshold as a logit
+ *      (ops.logit_threshold); no sigmoid is evaluated on the device;
+ *   4. greedy NMS in the selection order, per image and level on its own, with
+ *      torchvision's test (double)(inter / union) > nms_thresh, stopped at post_nms kept;
+ *   5. merge: the kept boxes of an image by (logit descending, level ascending, a ascending);
+ *      the first post_nms are written, count[n] is how many.
+ * Outputs, every element stored exactly once per call: boxes fp32 [N,post,4] (padding 0),
+ * logits fp32 [N,post] (-inf), levels / anchor_idx int32 [N,post] (-1), count int32 [N],
+ * rois fp32 [N*post,5] rows (n, x1, y1, x2, y2), a padding row (-1, 0, 0, 0, 0).
+ * Limits (FRCNN_EINVAL with a message, before any launch, like NULLs, misaligned pointers
+ * and a short workspace): 1 <= L <= 8, 1 <= N <= 1024, 1 <= K <= 32, H, W >= 1,
+ * K*H*W < 2^24, (H-1)*stride_h and (W-1)*stride_w < 2^24, strides >= 1,
+ * 1 <= pre_nms <= 2048, 1 <= post_nms <= 4096.  The workspace is stream-ordered scratch,
+ * 256-byte aligned; nothing in it needs to be initialised. */
+size_t frcnn_propose_multi_workspace_size(int n_levels, int N, int K, const int* H, const int* W, int pre_nms,
+                                          int post_nms);
+int frcnn_propose_multi_t(int dtype, int n_levels, const void* const* objectness, const void* const* deltas,
+                          const float* const* anchor_bases, const int* H, const int* W, const int* stride_h,
+                          const int* stride_w, int N, int K, const float* image_sizes, int pre_nms, int post_nms,
+                          double nms_thresh, float logit_thresh, float min_size, float* boxes, float* logits,
+                          int32_t* levels, int32_t* anchor_idx, int32_t* count, float* rois, void* workspace,
+                          size_t ws_bytes, void* stream);
+/* The kernels a call of this shape launches, in order; the selection kernel lists the branch
+ * each level takes: "sort" (K*H*W <= 2048, the level is sorted whole) or "select" (radix select):
+ * "fpn_select_decode_kernel<ElemF16>[select,sort] fpn_nms_mask_kernel fpn_sweep_kernel fpn_merge_kernel". */
+int frcnn_propose_multi_kernel(int dtype, int n_levels, int N, int K, const int* H, const int* W, int pre_nms,
+                               int post_nms, char* name, size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

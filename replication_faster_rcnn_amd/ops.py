@@ -18,6 +18,11 @@
   RoIAlign"); ``roi_align``'s input rule.
 * ``propose(...)`` -- the batched proposal layer (nets/rpn.py:47-79 over all
   images at once, replacing the per-image loop nets/rpn.py:131-136).
+* ``propose_multilevel(...)`` -- the FPN proposal layer, torchvision's
+  ``RegionProposalNetwork.filter_proposals`` over a pyramid of RPN head outputs
+  (no reference counterpart; DESIGN.md §3 "FPN proposals"), with
+  ``pyramid_anchor_bases`` / ``pyramid_anchors`` (torchvision's ``AnchorGenerator``)
+  and ``logit_threshold`` (its score threshold as a test on the raw logit).
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
   detections for the whole batch (no reference counterpart; DESIGN.md
   "Detections").
@@ -51,7 +56,7 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   types").  ``boxes`` / ``rois`` / ``roi_inds`` stay fp32, ``argmax`` int32.
   The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
-* The hot-path ops on device tensors (``propose``, ``roi_transform``,
+* The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``roi_transform``,
   ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
@@ -680,8 +685,264 @@ def propose(scores: torch.Tensor, deltas: torch.Tensor, *, img_w: float, img_h: 
     return rois, idx, cnt
 
 
+# -------------------------------------------------------------- FPN proposals
+FPN_MAX_LEVELS, FPN_MAX_K, FPN_MAX_PRE, FPN_MAX_POST, FPN_MAX_N = 8, 32, 2048, 4096, 1024
+FPN_SORT_CAP = 2048           # a level of at most this many anchors is sorted whole ("sort"), a larger one "select"
+_logit_thr_cache = {}         # score_thresh -> logit threshold
+_fpn_cache = {}               # shape key -> (H, W, stride_h, stride_w host arrays, workspace bytes)
+_fpn_sizes_cache = {}         # (h, w, N, device index) -> fp32 [N, 2] device tensor
+
+
+def pyramid_anchor_bases(sizes, aspect_ratios, device=None):
+    """torchvision's ``AnchorGenerator.generate_anchors`` in fp32 with torch CPU ops:
+    ``h_ratios = sqrt(ratios)``, ``w_ratios = 1 / h_ratios``, ``base = stack([-ws, -hs, ws,
+    hs], 1) / 2`` rounded, rows ratio-major.  ``sizes`` is one level's tuple of numbers (-> one
+    [K, 4] tensor) or a tuple of such tuples, one per level (-> a list); ``aspect_ratios``
+    likewise, a flat tuple serving every level.  ``device``: where the result goes (default:
+    the CPU; the op wants its bases on the device)."""
+    def one(scales, ratios):
+        s = torch.as_tensor(tuple(scales), dtype=torch.float32)
+        r = torch.as_tensor(tuple(ratios), dtype=torch.float32)
+        h_ratios = torch.sqrt(r)
+        w_ratios = 1 / h_ratios
+        ws = (w_ratios[:, None] * s[None, :]).view(-1)
+        hs = (h_ratios[:, None] * s[None, :]).view(-1)
+        base = (torch.stack([-ws, -hs, ws, hs], dim=1) / 2).round()
+        return base if device is None else base.to(device)
+
+    sizes = tuple(sizes)
+    if not sizes:
+        raise RuntimeError("pyramid_anchor_bases: sizes is empty")
+    if not isinstance(sizes[0], (tuple, list)):
+        return one(sizes, aspect_ratios)
+    ratios = tuple(aspect_ratios)
+    if not isinstance(ratios[0], (tuple, list)):
+        ratios = (ratios,) * len(sizes)
+    if len(ratios) != len(sizes):
+        raise RuntimeError(f"pyramid_anchor_bases: {len(sizes)} levels of sizes but {len(ratios)} of aspect_ratios")
+    return [one(s, r) for s, r in zip(sizes, ratios)]
+
+
+def pyramid_anchors(anchor_bases, strides, grid_sizes):
+    """torchvision's ``AnchorGenerator.grid_anchors`` with torch CPU ops: per level an fp32
+    [H*W*K, 4] tensor, anchor ``(y*W + x)*K + k = base[k] + (x*stride_w, y*stride_h, x*stride_w,
+    y*stride_h)``, one fp32 addition per coordinate.  ``strides``: (stride_h, stride_w) per
+    level; ``grid_sizes``: (H, W) per level.  For tests and target assignment; the op forms the
+    same anchors in registers."""
+    out = []
+    for base, (sh, sw), (H, W) in zip(anchor_bases, strides, grid_sizes):
+        b = base.detach().to("cpu", torch.float32)
+        xs = (torch.arange(int(W), dtype=torch.int64) * int(sw)).to(torch.float32)
+        ys = (torch.arange(int(H), dtype=torch.int64) * int(sh)).to(torch.float32)
+        sy, sx = torch.meshgrid(ys, xs, indexing="ij")
+        shifts = torch.stack([sx.reshape(-1), sy.reshape(-1), sx.reshape(-1), sy.reshape(-1)], dim=1)
+        out.append((shifts[:, None, :] + b[None, :, :]).reshape(-1, 4))
+    return out
+
+
+def _f32_ordinal(x: float) -> int:
+    """Position of an fp32 value in the total order -inf .. -0 < +0 .. +inf (an int)."""
+    i = int(torch.tensor(x, dtype=torch.float32).view(torch.int32))
+    return i if i >= 0 else -(i & 0x7FFFFFFF) - 1
+
+
+def _f32_from_ordinal(o: int) -> float:
+    i = o if o >= 0 else ((-o - 1) | 0x80000000) - (1 << 32)
+    return float(torch.tensor(i, dtype=torch.int32).view(torch.float32))
+
+
+def logit_threshold(score_thresh: float) -> float:
+    """The score threshold of torchvision's ``scores >= score_thresh`` as a threshold on the raw
+    logit: the smallest fp32 ``t`` with ``torch.sigmoid(t) >= score_thresh`` on the CPU, found by
+    bisection over the fp32 bit patterns from -inf to +inf (torch's CPU sigmoid is nondecreasing),
+    so ``logit >= t`` is the same test and the kernels evaluate no sigmoid.  ``score_thresh <= 0``
+    gives -inf (every non-NaN logit passes), one above 1 NaN (none does).  Host only; cached."""
+    key = float(score_thresh)
+    t = _logit_thr_cache.get(key)
+    if t is None:
+        if key != key or key > 1.0:
+            t = float("nan")
+        elif key <= 0.0:
+            t = float("-inf")
+        else:
+            thr = torch.tensor(key, dtype=torch.float32)
+
+            def passes(o):
+                return bool(torch.sigmoid(torch.tensor(_f32_from_ordinal(o), dtype=torch.float32)) >= thr)
+
+            lo, hi = _f32_ordinal(float("-inf")), _f32_ordinal(float("inf"))   # sigmoid 0 < thr <= 1 = sigmoid(+inf)
+            if not passes(hi):          # a threshold that rounds above 1 in fp32 cannot occur; keep the rule total
+                t = float("nan")
+            else:
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    if passes(mid):
+                        hi = mid
+                    else:
+                        lo = mid
+                t = _f32_from_ordinal(hi)
+        _logit_thr_cache[key] = t
+    return t
+
+
+def _fpn_tensor(name, t, dtype, shape):
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous()
+            or tuple(t.shape) != tuple(shape)):
+        got = (f"{'contiguous' if t.is_contiguous() else 'strided'} {t.dtype} {t.device.type} tensor of shape "
+               f"{list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__)
+        raise RuntimeError(f"propose_multilevel: {name} must be a contiguous {dtype} device tensor of shape "
+                           f"{list(shape)}; got a {got}")
+
+
+def _fpn_shape_key(op, objectness, strides, pre, post):
+    """(L, N, K, ((H, W, stride_h, stride_w), ...), pre, post) with the limits checked."""
+    if not isinstance(objectness, (list, tuple)) or not 1 <= len(objectness) <= FPN_MAX_LEVELS:
+        raise RuntimeError(f"{op}: objectness must be a list of 1 to {FPN_MAX_LEVELS} tensors [N, K, H, W]")
+    L = len(objectness)
+    o0 = objectness[0]
+    if not isinstance(o0, torch.Tensor) or o0.dim() != 4:
+        raise RuntimeError(f"{op}: objectness[0] must be a device tensor of shape [N, K, H, W]")
+    N, K = int(o0.shape[0]), int(o0.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: objectness: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= K <= FPN_MAX_K:
+        raise RuntimeError(f"{op}: objectness: K must be in [1, {FPN_MAX_K}]; got {K}")
+    if not isinstance(strides, (list, tuple)) or len(strides) != L:
+        raise RuntimeError(f"{op}: strides must list one (stride_h, stride_w) per level ({L})")
+    pre, post = int(pre), int(post)
+    if not 1 <= pre <= FPN_MAX_PRE:
+        raise RuntimeError(f"{op}: pre_nms_top_n must be in [1, {FPN_MAX_PRE}]; got {pre}")
+    if not 1 <= post <= FPN_MAX_POST:
+        raise RuntimeError(f"{op}: post_nms_top_n must be in [1, {FPN_MAX_POST}]; got {post}")
+    levels = []
+    for l, (o, s) in enumerate(zip(objectness, strides)):
+        if not isinstance(o, torch.Tensor) or o.dim() != 4:
+            raise RuntimeError(f"{op}: objectness[{l}] must be a device tensor of shape [N, K, H, W]")
+        try:
+            sh, sw = int(s[0]), int(s[1])
+        except (TypeError, ValueError, IndexError):
+            raise RuntimeError(f"{op}: strides[{l}] must be (stride_h, stride_w) ints; got {s!r}") from None
+        H, W = int(o.shape[2]), int(o.shape[3])
+        if H < 1 or W < 1 or K * H * W >= 1 << 24:
+            raise RuntimeError(f"{op}: objectness[{l}]: H, W >= 1 and K*H*W < 2^24 are required; got {list(o.shape)}")
+        if sh < 1 or sw < 1 or (H - 1) * sh >= 1 << 24 or (W - 1) * sw >= 1 << 24:
+            raise RuntimeError(f"{op}: strides[{l}] = {(sh, sw)}: strides >= 1 and (H-1)*stride_h, (W-1)*stride_w "
+                               "below 2^24 are required")
+        levels.append((H, W, sh, sw))
+    return L, N, K, tuple(levels), pre, post
+
+
+def propose_multilevel_kernel(objectness_shapes, dtype, pre_nms_top_n, post_nms_top_n) -> str:
+    """frcnn_propose_multi_kernel: the kernels a call on maps of these [N, K, H, W] shapes
+    launches, with the selection branch of every level ("sort" | "select").  Host only."""
+    lib = _lib.load(require_gpu=False)
+    shapes = [tuple(int(v) for v in s) for s in objectness_shapes]
+    L = len(shapes)
+    H = (_lib.I32 * L)(*[s[2] for s in shapes])
+    W = (_lib.I32 * L)(*[s[3] for s in shapes])
+    buf = _lib.ctypes.create_string_buffer(256)
+    _lib.check(lib.frcnn_propose_multi_kernel(_lib.dtype_code(dtype), L, shapes[0][0], shapes[0][1], H, W,
+                                              int(pre_nms_top_n), int(post_nms_top_n), buf, 256),
+               "propose_multi_kernel")
+    return buf.value.decode()
+
+
+def propose_multilevel(objectness, deltas, anchor_bases, strides, image_sizes, *, pre_nms_top_n: int,
+                       post_nms_top_n: int, nms_thresh: float = 0.7, score_thresh: float = 0.0,
+                       min_size: float = 1e-3, out=None, workspace=None):
+    """The FPN proposal layer: torchvision's ``RegionProposalNetwork.filter_proposals`` with
+    ``BoxCoder(weights=(1, 1, 1, 1))`` for the whole batch and pyramid, four launches, no host
+    synchronisation (frcnn_propose_multi_t; DESIGN.md §3 "FPN proposals" is the contract).
+
+    ``objectness``: L tensors [N, K, H_l, W_l]; ``deltas``: L tensors [N, 4K, H_l, W_l] (channel
+    4k + c) -- an ``RPNHead``'s conv outputs as they are, all fp32, float16 or bfloat16, read in
+    place; ``anchor_bases``: L fp32 device tensors [K, 4] (``pyramid_anchor_bases``);
+    ``strides``: L host (stride_h, stride_w); ``image_sizes``: fp32 device tensor [N, 2] of
+    (h, w), or one host (h, w) for every image (expanded once, cached).
+
+    Per image and level: the first ``min(pre_nms_top_n, A_l)`` anchors in torch's stable
+    descending order of the raw logit (NaN first, -0 == +0, ties by anchor index) are decoded,
+    clipped to the image, filtered (``min_size``; ``sigmoid(logit) >= score_thresh`` as a test
+    on the logit, ``logit_threshold``) and swept by greedy NMS; the kept boxes of all levels are
+    merged by (logit descending, level, anchor index) and the first ``post_nms_top_n`` written.
+
+    Returns padded ``(boxes [N, post, 4], logits [N, post] (-inf), levels int32 [N, post] (-1),
+    anchor_idx int32 [N, post] (-1), count int32 [N], rois [N*post, 5])``; a padding row of
+    ``rois`` is (-1, 0, 0, 0, 0), which ``multiscale_roi_align`` / ``roi_align`` pool to zeros.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device or a strided view raises
+    RuntimeError naming the argument before any launch.  ``out``: the six outputs, caller-owned;
+    ``workspace``: a uint8 device tensor of at least the cached size."""
+    op = "propose_multilevel"
+    lib = _lib.load()
+    L, N, K, levels, pre, post = key0 = _fpn_shape_key(op, objectness, strides, pre_nms_top_n, post_nms_top_n)
+    if not isinstance(deltas, (list, tuple)) or len(deltas) != L:
+        raise RuntimeError(f"{op}: deltas must list one tensor per level ({L})")
+    if not isinstance(anchor_bases, (list, tuple)) or len(anchor_bases) != L:
+        raise RuntimeError(f"{op}: anchor_bases must list one tensor per level ({L})")
+    code = _lib.prediction_dtype_code(op, [(f"objectness[{l}]", t) for l, t in enumerate(objectness)] +
+                                      [(f"deltas[{l}]", t) for l, t in enumerate(deltas)])
+    dt = objectness[0].dtype
+    dev = objectness[0].device
+    for l, (H, W, _, _) in enumerate(levels):
+        _fpn_tensor(f"objectness[{l}]", objectness[l], dt, (N, K, H, W))
+        _fpn_tensor(f"deltas[{l}]", deltas[l], dt, (N, 4 * K, H, W))
+        _fpn_tensor(f"anchor_bases[{l}]", anchor_bases[l], torch.float32, (K, 4))
+    if isinstance(image_sizes, torch.Tensor):
+        _fpn_tensor("image_sizes", image_sizes, torch.float32, (N, 2))
+        sizes = image_sizes
+    else:
+        try:
+            hw = (float(image_sizes[0]), float(image_sizes[1]))
+            if len(image_sizes) != 2:
+                raise ValueError
+        except (TypeError, ValueError, IndexError):
+            raise RuntimeError(f"{op}: image_sizes must be an fp32 device tensor [N, 2] of (h, w) or one host "
+                               f"(h, w); got {image_sizes!r}") from None
+        skey = (hw, N, dev.index)
+        sizes = _fpn_sizes_cache.get(skey)
+        if sizes is None:
+            sizes = torch.tensor([hw] * N, dtype=torch.float32).to(dev)
+            _fpn_sizes_cache[skey] = sizes
+    cached = _fpn_cache.get(key0)
+    if cached is None:
+        Hs = (_lib.I32 * L)(*[v[0] for v in levels])
+        Ws = (_lib.I32 * L)(*[v[1] for v in levels])
+        shs = (_lib.I32 * L)(*[v[2] for v in levels])
+        sws = (_lib.I32 * L)(*[v[3] for v in levels])
+        need = int(lib.frcnn_propose_multi_workspace_size(L, N, K, Hs, Ws, pre, post))
+        if need == 0:
+            raise RuntimeError(f"{op}: {lib.frcnn_last_error().decode()}")
+        cached = (Hs, Ws, shs, sws, need)
+        _fpn_cache[key0] = cached
+    Hs, Ws, shs, sws, need = cached
+    shapes = (((N, post, 4), torch.float32, "boxes"), ((N, post), torch.float32, "logits"),
+              ((N, post), torch.int32, "levels"), ((N, post), torch.int32, "anchor_idx"),
+              ((N,), torch.int32, "count"), ((N * post, 5), torch.float32, "rois"))
+    if out is None:
+        outs = tuple(torch.empty(s, dtype=d, device=dev) for s, d, _ in shapes)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != 6:
+            raise RuntimeError(f"{op}: out must be the six outputs (boxes, logits, levels, anchor_idx, count, rois)")
+        outs = tuple(out)
+        for i, (s, d, nm) in enumerate(shapes):
+            _fpn_tensor(f"out[{i}] ({nm})", outs[i], d, s)
+    ws = workspace if workspace is not None else _lib.cached_workspace("propose_multilevel", need, dev)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous()
+            or ws.numel() < need):
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 device tensor of at least {need} B")
+    P = _lib.P
+    _lib.check(lib.frcnn_propose_multi_t(code, L, (P * L)(*[t.data_ptr() for t in objectness]),
+                                         (P * L)(*[t.data_ptr() for t in deltas]),
+                                         (P * L)(*[t.data_ptr() for t in anchor_bases]), Hs, Ws, shs, sws, N, K,
+                                         _lib.ptr(sizes), pre, post, float(nms_thresh), logit_threshold(score_thresh),
+                                         float(min_size), *[_lib.ptr(t) for t in outs], _lib.ptr(ws), ws.numel(),
+                                         _lib.stream_ptr()), op)
+    return outs
+
+
 # ----------------------------------------------------------------- detections
-REG_MEAN = (0.0, 0.0, 0.0, 0.0)   # utils/utils.py:272 (ProposalTargetCreator's normalisation)
+REG_MEAN =(0.0, 0.0, 0.0, 0.0)   # utils/utils.py:272 (ProposalTargetCreator's normalisation)
 REG_STD = (0.1, 0.1, 0.2, 0.2)
 _detect_cache = {}  # host reg_mean / reg_std arrays + workspace size per shape (built once)
 

@@ -118,3 +118,41 @@ class RPN(nn.Module):
             anchors = anchors.cpu().numpy()
         self.anchors = anchors
         return cls, reg.to(x.device), rois, roi_inds, anchors
+
+
+class MultiLevelProposals(nn.Module):
+    """torchvision's ``RegionProposalNetwork.filter_proposals`` for an FPN RPN head on
+    ``ops.propose_multilevel``.  ``pre_nms_top_n`` / ``post_nms_top_n`` are dicts with the keys
+    ``training`` and ``testing``, as torchvision's are; ``forward`` picks by ``self.training``
+    and returns the op's padded tuple with no host sync.  ``as_lists=True`` returns
+    torchvision's ``(boxes list, scores list)`` instead, ``scores = sigmoid(logits)``; the one
+    read of ``count`` that needs is the only synchronisation."""
+
+    def __init__(self, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh=0.0, min_size=1e-3):
+        super().__init__()
+        for name, d in (("pre_nms_top_n", pre_nms_top_n), ("post_nms_top_n", post_nms_top_n)):
+            if not isinstance(d, dict) or "training" not in d or "testing" not in d:
+                raise RuntimeError(f"MultiLevelProposals: {name} must be a dict with the keys 'training' and 'testing'")
+        self._pre_nms_top_n = dict(pre_nms_top_n)
+        self._post_nms_top_n = dict(post_nms_top_n)
+        self.nms_thresh = nms_thresh
+        self.score_thresh = score_thresh
+        self.min_size = min_size
+
+    def pre_nms_top_n(self):
+        return self._pre_nms_top_n["training" if self.training else "testing"]
+
+    def post_nms_top_n(self):
+        return self._post_nms_top_n["training" if self.training else "testing"]
+
+    def forward(self, objectness, deltas, anchor_bases, strides, image_sizes, as_lists=False):
+        res = ops.propose_multilevel(objectness, deltas, anchor_bases, strides, image_sizes,
+                                     pre_nms_top_n=self.pre_nms_top_n(), post_nms_top_n=self.post_nms_top_n(),
+                                     nms_thresh=self.nms_thresh, score_thresh=self.score_thresh,
+                                     min_size=self.min_size)
+        if not as_lists:
+            return res
+        boxes, logits, _, _, count, _ = res
+        counts = count.tolist()  # the one host sync: the lists' lengths are data-dependent
+        return ([boxes[i, :c] for i, c in enumerate(counts)],
+                [torch.sigmoid(logits[i, :c]) for i, c in enumerate(counts)])
