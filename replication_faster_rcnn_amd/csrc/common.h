@@ -93,14 +93,51 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
     return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
-__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+// The wave-wide reduction and inclusive scan of every unit but roi_pool.hip.
+// op(own, other) is applied in exactly this order and these loop shapes, so a
+// floating-point result is fixed by them: the butterfly goes from 32 down to 1
+// and leaves the result in every lane; the scan goes from 1 up to 32 (lane =
+// threadIdx.x & 63: one-dimensional workgroups of whole waves).
+struct op_add {
+    template <class T> __device__ T operator()(T a, T b) const { return a + b; }
+};
+struct op_or {
+    template <class T> __device__ T operator()(T a, T b) const { return a | b; }
+};
+struct op_max {  // written out, not fmax: what a NaN does is part of the result
+    template <class T> __device__ T operator()(T a, T b) const { return a > b ? a : b; }
+};
+
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     return v;
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+template <class T, class Op>
+__device__ __forceinline__ T wave_scan_incl(T v, Op op) {
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v = op(v, u);
+    }
     return v;
+}
+
+// # of keys < key in the ascending run sorted[0, len)
+template <class T>
+__device__ __forceinline__ int count_before(const T* sorted, int len, T key) {
+    int lo = 0, n = len;
+    while (n > 0) {
+        const int h = n >> 1;
+        if (sorted[lo + h] < key) {
+            lo += h + 1;
+            n -= h + 1;
+        } else {
+            n = h;
+        }
+    }
+    return lo;
 }
 
 __device__ __forceinline__ uint64_t lanemask_lt() {

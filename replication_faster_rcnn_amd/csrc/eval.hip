@@ -24,13 +24,14 @@
 //                         insertion order the input already has), five 8-bit
 //                         passes of histogram / scan / scatter.
 //   eval_ap_kernel      : one workgroup per class: its segment of the sorted
-//                         keys by binary search on the class field, the tp / fp
-//                         totals, then one pass from the last record to the
-//                         first with running tp / fp, suffix maximum of the
-//                         precision and the integration.
+//                         keys by binary search on the class field, then
+//                         ev_pr_walk (eval_common.h: the tp / fp totals and one
+//                         pass from the last record to the first with running
+//                         tp / fp and the suffix maximum of the precision),
+//                         integrating at each record.
 //   eval_map_kernel     : mean of the non-NaN APs in ascending class order.
-// The limits, the header step and the sort's host entry (eval_sort_keys) are
-// shared with the COCO-style evaluation (eval_common.h, eval_coco.hip).
+// The limits, the header step, the walk and the sort's host entry
+// (eval_sort_keys) are shared with the COCO-style evaluation (eval_common.h, eval_coco.hip).
 // Integer atomics only (LDS claim minima, npos counts): every result is
 // independent of the order workgroups and waves run in.
 #include <cmath>
@@ -212,11 +213,7 @@ __global__ __launch_bounds__(kScanThreads) void eval_sort_scan_kernel(uint32_t* 
     const int lo = min(len, tid * per), hi = min(len, lo + per);
     uint32_t s = 0;
     for (int i = lo; i < hi; ++i) s += hist[i];
-    uint32_t v = s;  // inclusive scan over the threads
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
+    const uint32_t v = wave_scan_incl(s, op_add{});  // inclusive scan over the threads
     if (lane == 63) wsum[wid] = v;
     __syncthreads();
     uint32_t pre = 0;
@@ -296,83 +293,24 @@ __global__ __launch_bounds__(kEvThreads) void eval_ap_kernel(int C, int n, const
         return;
     }
     const double npos = static_cast<double>(npos_ll);
-    const int lo = ev_lower_bound(sorted, n, static_cast<uint64_t>(c) << 56);
-    const int hi = ev_lower_bound(sorted, n, static_cast<uint64_t>(c + 1) << 56);
+    const int lo = count_before(sorted, n, static_cast<uint64_t>(c) << 56);
+    const int hi = count_before(sorted, n, static_cast<uint64_t>(c + 1) << 56);
     const int nc = hi - lo;
 
-    // ---- totals: tp in the high word, fp in the low word
-    unsigned long long acc = 0;
-    for (int p = tid; p < nc; p += kEvThreads) {
-        const int f = ev_flag(rec_flag, sorted[lo + p], n);
-        acc += f == 1 ? (1ull << 32) : (f == 0 ? 1ull : 0ull);
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) wtot[wid] = acc;
-    __syncthreads();
-    unsigned long long carry = 0;  // tp / fp up to and including the last record not yet walked
-    for (int w = 0; w < kEvWaves; ++w) carry += wtot[w];
-    __syncthreads();
-
-    // ---- from the last record to the first: thread order = descending record order
-    double cmax = 0.0;  // mpre's closing 0, then the suffix maximum of the records walked
-    double sum = 0.0;
-    double pm[11];
-    for (int i = 0; i < 11; ++i) pm[i] = 0.0;
-    for (int p0 = 0; p0 < nc; p0 += kEvThreads) {
-        const int p = p0 + tid;
-        const bool valid = p < nc;
-        int f = -1;
-        if (valid) f = ev_flag(rec_flag, sorted[hi - 1 - p], n);
-        const unsigned long long mine = f == 1 ? (1ull << 32) : (f == 0 ? 1ull : 0ull);
-        unsigned long long v = mine;  // inclusive scan: this record and the later ones of the chunk
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wtot[wid] = v;
-        __syncthreads();
-        unsigned long long pre = 0, chunk = 0;
-        for (int w = 0; w < kEvWaves; ++w) {
-            pre += w < wid ? wtot[w] : 0ull;
-            chunk += wtot[w];
-        }
-        const unsigned long long at = carry - (pre + v - mine);  // running sums at this record
-        const double tp = static_cast<double>(at >> 32);
-        const double all = static_cast<double>((at >> 32) + (at & 0xFFFFFFFFull));
-        const double prec = valid ? tp / (all < 1.0 ? 1.0 : all) : 0.0;
-        const double rec = tp / npos;
-        double m = prec;  // inclusive maximum in thread order = suffix maximum in record order
-        for (int o = 1; o < 64; o <<= 1) {
-            const double u = __shfl_up(m, o, 64);
-            if (lane >= o) m = ev_dmax(m, u);
-        }
-        if (lane == 63) wmax[wid] = m;
-        __syncthreads();
-        double pmx = cmax, cm = cmax;
-        for (int w = 0; w < kEvWaves; ++w) {
-            pmx = w < wid ? ev_dmax(pmx, wmax[w]) : pmx;
-            cm = ev_dmax(cm, wmax[w]);
-        }
-        m = ev_dmax(m, pmx);
-        if (valid) {
-            if (use_07) {
-                for (int i = 0; i < 11; ++i)
-                    if (rec >= static_cast<double>(i) * 0.1) pm[i] = ev_dmax(pm[i], prec);
-            } else if (f == 1) {  // mrec changes exactly at a TP
-                const double d = rec - (tp - 1.0) / npos;
-                sum = sum + d * m;
-            }
-        }
-        carry -= chunk;
-        cmax = cm;
-        __syncthreads();
-    }
-
-    if (use_07) {
+    // ---- the walk from the last record to the first (ev_pr_walk), then the integration
+    const auto flag = [&](int p) { return ev_flag(rec_flag, sorted[lo + p], n); };
+    const auto prec_of = [](int, double tp, double all) { return tp / (all < 1.0 ? 1.0 : all); };
+    if (use_07) {  // the largest precision at a recall of at least i / 10
+        double pm[11];
+        for (int i = 0; i < 11; ++i) pm[i] = 0.0;
+        ev_pr_walk(nc, wtot, wmax, flag, prec_of, [&](int, double tp, double prec, double) {
+            const double rec = tp / npos;
+            for (int i = 0; i < 11; ++i)
+                if (rec >= static_cast<double>(i) * 0.1) pm[i] = ev_dmax(pm[i], prec);
+        });
         double total = 0.0;
         for (int i = 0; i < 11; ++i) {
-            double v = pm[i];
-            for (int o = 32; o > 0; o >>= 1) v = ev_dmax(v, __shfl_xor(v, o, 64));
+            double v = wave_reduce(pm[i], op_max{});
             if (lane == 0) wred[wid] = v;
             __syncthreads();
             v = wred[0];
@@ -381,8 +319,14 @@ __global__ __launch_bounds__(kEvThreads) void eval_ap_kernel(int C, int n, const
             total = total + v / 11.0;
         }
         if (tid == 0) ap[c] = total;
-    } else {
-        for (int o = 32; o > 0; o >>= 1) sum = sum + __shfl_xor(sum, o, 64);
+    } else {  // the area under the envelope: mrec changes exactly at a TP
+        double sum = 0.0;
+        ev_pr_walk(nc, wtot, wmax, flag, prec_of, [&](int f, double tp, double, double m) {
+            if (f != 1) return;
+            const double d = tp / npos - (tp - 1.0) / npos;
+            sum = sum + d * m;
+        });
+        sum = wave_reduce(sum, op_add{});
         if (lane == 0) wred[wid] = sum;
         __syncthreads();
         if (tid == 0) {

@@ -22,10 +22,11 @@
 //   eval_sort_*_kernel     : eval.hip's stable radix sort over the same key bits.
 //   coco_gather_kernel     : the record words in sorted order.
 //   coco_accumulate_kernel : one workgroup per (class, area range, maxDet,
-//                            threshold): its class segment by binary search, the
-//                            tp / fp totals, then one pass from the last record
-//                            to the first with running integer tp / fp and the
-//                            suffix maximum of the precision.  The record at
+//                            threshold): its class segment by binary search,
+//                            then ev_pr_walk (eval_common.h, shared with
+//                            eval.hip): the tp / fp totals and one pass from the
+//                            last record to the first with running tp / fp and
+//                            the suffix maximum of the precision.  The record at
 //                            which tp reaches j serves the recall thresholds
 //                            (j-1)/npig < R[r] <= j/npig.
 //   coco_summary_kernel    : the twelve stats and ap_per_class, one workgroup
@@ -303,8 +304,6 @@ __global__ __launch_bounds__(kEvThreads) void coco_advance_kernel(int N, int M, 
 }
 
 // ----------------------------------------------------------------- accumulate
-__device__ __forceinline__ double co_dmax(double a, double b) { return a > b ? a : b; }
-
 // The record words in sorted order, so that the 120 passes over a class segment read them in sequence.  A
 // record index is below n by construction; a key that is not one (a caller's n over the records held) reads as
 // rank "out".
@@ -338,7 +337,7 @@ __global__ __launch_bounds__(kEvThreads) void coco_accumulate_kernel(int C, int 
     __shared__ unsigned long long wtot[kEvWaves];
     __shared__ double wmax[kEvWaves];
     __shared__ double pout[kCoR];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     int b = blockIdx.x;
     const int t = b % kCoT;
     b /= kCoT;
@@ -360,63 +359,18 @@ __global__ __launch_bounds__(kEvThreads) void coco_accumulate_kernel(int C, int 
     const double npig = static_cast<double>(npig_ll);
     const double* R = tables + kCoTabR;
     if (tid < kCoR) pout[tid] = 0.0;
-    const int lo = n > 0 ? ev_lower_bound(sorted, n, static_cast<uint64_t>(c) << 56) : 0;
-    const int hi = n > 0 ? ev_lower_bound(sorted, n, static_cast<uint64_t>(c + 1) << 56) : 0;
+    const int lo = n > 0 ? count_before(sorted, n, static_cast<uint64_t>(c) << 56) : 0;
+    const int hi = n > 0 ? count_before(sorted, n, static_cast<uint64_t>(c + 1) << 56) : 0;
     const int nc = hi - lo;
 
-    // ---- totals: tp in the high word, fp in the low word
-    unsigned long long acc = 0;
-    for (int p = tid; p < nc; p += kEvThreads) {
-        const int f = co_flag(sorted_bits, lo + p, a, t, max_det);
-        acc += f == 1 ? (1ull << 32) : (f == 0 ? 1ull : 0ull);
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) wtot[wid] = acc;
-    __syncthreads();
-    unsigned long long carry = 0;  // tp / fp up to and including the last record not yet walked
-    for (int w = 0; w < kEvWaves; ++w) carry += wtot[w];
-    __syncthreads();
-    if (tid == 0) *rout = static_cast<double>(carry >> 32) / npig;
-
-    // ---- from the last record to the first: thread order = descending record order
-    double cmax = 0.0;  // suffix maximum of the records walked
-    for (int p0 = 0; p0 < nc; p0 += kEvThreads) {
-        const int p = p0 + tid;
-        const bool valid = p < nc;
-        int f = -1;
-        if (valid) f = co_flag(sorted_bits, hi - 1 - p, a, t, max_det);
-        const unsigned long long mine = f == 1 ? (1ull << 32) : (f == 0 ? 1ull : 0ull);
-        unsigned long long v = mine;  // inclusive scan: this record and the later ones of the chunk
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wtot[wid] = v;
-        __syncthreads();
-        unsigned long long pre = 0, chunk = 0;
-        for (int w = 0; w < kEvWaves; ++w) {
-            pre += w < wid ? wtot[w] : 0ull;
-            chunk += wtot[w];
-        }
-        const unsigned long long at = carry - (pre + v - mine);  // running sums at this record
-        const long long tpi = static_cast<long long>(at >> 32);
-        const double tp = static_cast<double>(tpi);
-        const double all = static_cast<double>((at >> 32) + (at & 0xFFFFFFFFull));
-        const double prec = f == 1 ? tp / (all + kCoEps) : 0.0;  // the maximum is always at a TP
-        double mx = prec;  // inclusive maximum in thread order = suffix maximum in record order
-        for (int o = 1; o < 64; o <<= 1) {
-            const double u = __shfl_up(mx, o, 64);
-            if (lane >= o) mx = co_dmax(mx, u);
-        }
-        if (lane == 63) wmax[wid] = mx;
-        __syncthreads();
-        double pmx = cmax, cm = cmax;
-        for (int w = 0; w < kEvWaves; ++w) {
-            pmx = w < wid ? co_dmax(pmx, wmax[w]) : pmx;
-            cm = co_dmax(cm, wmax[w]);
-        }
-        mx = co_dmax(mx, pmx);
-        if (f == 1) {  // tp reaches tpi here: the recall thresholds in ((tpi-1)/npig, tpi/npig]
+    // ---- the walk from the last record to the first (ev_pr_walk).  The maximum is always at a TP;
+    // the record at which tp reaches tpi serves the recall thresholds in ((tpi-1)/npig, tpi/npig].
+    const unsigned long long total = ev_pr_walk(
+        nc, wtot, wmax, [&](int p) { return co_flag(sorted_bits, lo + p, a, t, max_det); },
+        [](int f, double tp, double all) { return f == 1 ? tp / (all + kCoEps) : 0.0; },
+        [&](int f, double tp, double, double mx) {
+            if (f != 1) return;
+            const long long tpi = static_cast<long long>(tp);
             const double rc = tp / npig;
             const double rp = (tp - 1.0) / npig;
             int r = 0;
@@ -426,11 +380,8 @@ __global__ __launch_bounds__(kEvThreads) void coco_accumulate_kernel(int C, int 
             }
             for (; r < kCoR && R[r] <= rc; ++r)
                 if (tpi == 1 || R[r] > rp) pout[r] = mx;
-        }
-        carry -= chunk;
-        cmax = cm;
-        __syncthreads();
-    }
+        });
+    if (tid == 0) *rout = static_cast<double>(total >> 32) / npig;
     __syncthreads();
     if (tid < kCoR) pbase[tid * pstride] = pout[tid];
 }
@@ -450,10 +401,8 @@ __device__ __forceinline__ double co_mean(const double* __restrict__ base, long 
             ++k;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        s = s + __shfl_xor(s, o, 64);
-        k += __shfl_xor(k, o, 64);
-    }
+    s = wave_reduce(s, op_add{});
+    k = wave_reduce(k, op_add{});
     if (lane == 0) {
         red_s[wid] = s;
         red_k[wid] = k;

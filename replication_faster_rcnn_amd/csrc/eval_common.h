@@ -1,7 +1,8 @@
 // What the two evaluation units share (eval.hip: PASCAL VOC, eval_coco.hip:
-// COCO-style): the limits, the accumulator's header step and the stable radix
-// sort of the record keys, which lives in eval.hip and is reached from
-// eval_coco.hip through the host entry below.
+// COCO-style): the limits, the accumulator's header step, the precision /
+// recall walk over a class segment (ev_pr_walk) and the stable radix sort of
+// the record keys, which lives in eval.hip and is reached from eval_coco.hip
+// through the host entry below.
 #pragma once
 
 #include "common.h"
@@ -21,11 +22,6 @@ __device__ __forceinline__ int ev_count(const int32_t* det_count, int n, int M) 
     return k < 0 ? 0 : (k > M ? M : k);
 }
 
-__device__ __forceinline__ long long ev_wave_sum(long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Sum of the clamped counts of all images (total) and of the images before n.
 __device__ __forceinline__ void ev_count_sums(const int32_t* det_count, int N, int M, int n, long long* red,
                                               long long* before, long long* total) {
@@ -36,8 +32,8 @@ __device__ __forceinline__ void ev_count_sums(const int32_t* det_count, int N, i
         t += k;
         b += i < n ? k : 0;
     }
-    b = ev_wave_sum(b);
-    t = ev_wave_sum(t);
+    b = wave_reduce(b, op_add{});
+    t = wave_reduce(t, op_add{});
     if (lane == 0) {
         red[wid] = b;
         red[kEvWaves + wid] = t;
@@ -75,13 +71,68 @@ __device__ __forceinline__ void ev_advance(int N, int M, long long cap, const in
     }
 }
 
-__device__ __forceinline__ int ev_lower_bound(const uint64_t* __restrict__ keys, int n, uint64_t v) {
-    int lo = 0, hi = n;  // first index with keys[i] >= v
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
+// The precision / recall walk over one class segment of nc records in descending
+// score order, by one workgroup of kEvThreads (eval.hip's AP, eval_coco.hip's
+// accumulate).  flag(p) is the flag of the segment's record p: 1 TP, 0 FP, -1
+// neither.  First the totals, tp in the high word and fp in the low word; then
+// from the last record to the first, kEvThreads at a time, thread order =
+// descending record order: a reversed inclusive scan gives the running tp and
+// tp + fp at each record (integers, exact in a double), prec_of(f, tp, all) its
+// precision, and an inclusive maximum carried from chunk to chunk the largest
+// precision of the record and every later one.  visit(f, tp, prec, suffix_max)
+// is called once per record.  Returns the totals.  wtot, wmax: kEvWaves words of
+// LDS each; every thread of the workgroup calls it.
+template <class Flag, class Prec, class Visit>
+__device__ __forceinline__ unsigned long long ev_pr_walk(int nc, unsigned long long* wtot, double* wmax, Flag flag,
+                                                         Prec prec_of, Visit visit) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const auto count_of = [](int f) { return f == 1 ? (1ull << 32) : (f == 0 ? 1ull : 0ull); };
+    unsigned long long acc = 0;
+    for (int p = tid; p < nc; p += kEvThreads) acc += count_of(flag(p));
+    acc = wave_reduce(acc, op_add{});
+    if (lane == 0) wtot[wid] = acc;
+    __syncthreads();
+    unsigned long long total = 0;
+    for (int w = 0; w < kEvWaves; ++w) total += wtot[w];
+    __syncthreads();
+
+    unsigned long long carry = total;  // tp / fp up to and including the last record not yet walked
+    double cmax = 0.0;                 // mpre's closing 0, then the suffix maximum of the records walked
+    for (int p0 = 0; p0 < nc; p0 += kEvThreads) {
+        const int p = p0 + tid;
+        const bool valid = p < nc;
+        int f = -1;
+        if (valid) f = flag(nc - 1 - p);
+        const unsigned long long mine = count_of(f);
+        // inclusive scan: this record and the later ones of the chunk
+        const unsigned long long v = wave_scan_incl(mine, op_add{});
+        if (lane == 63) wtot[wid] = v;
+        __syncthreads();
+        unsigned long long pre = 0, chunk = 0;
+        for (int w = 0; w < kEvWaves; ++w) {
+            pre += w < wid ? wtot[w] : 0ull;
+            chunk += wtot[w];
+        }
+        const unsigned long long at = carry - (pre + v - mine);  // running sums at this record
+        const double tp = static_cast<double>(at >> 32);
+        const double all = static_cast<double>((at >> 32) + (at & 0xFFFFFFFFull));
+        const double prec = valid ? prec_of(f, tp, all) : 0.0;
+        // inclusive maximum in thread order = suffix maximum in record order
+        double m = wave_scan_incl(prec, op_max{});
+        if (lane == 63) wmax[wid] = m;
+        __syncthreads();
+        double pmx = cmax, cm = cmax;
+        for (int w = 0; w < kEvWaves; ++w) {
+            pmx = w < wid ? op_max{}(pmx, wmax[w]) : pmx;
+            cm = op_max{}(cm, wmax[w]);
+        }
+        m = op_max{}(m, pmx);
+        if (valid) visit(f, tp, prec, m);
+        carry -= chunk;
+        cmax = cm;
+        __syncthreads();
     }
-    return lo;
+    return total;
 }
 
 // eval.hip: the stable LSD radix sort of n record keys over bits 24..63 (the low

@@ -7,8 +7,11 @@
 //       NCHW in their own dtype), sorted in LDS, then decoded, clipped and filtered;
 //       the survivors are compacted in rank order.  A level of at most kFpnSortCap
 //       anchors is sorted whole ("sort"); a larger one goes through an exact radix
-//       select that re-reads the logits once per digit ("select").
-//   fpn_nms_mask_kernel   chip-wide 64x64 column-form IoU tiles of every (image, level).
+//       select that re-reads the logits once per digit ("select"; hist_find,
+//       radix_select.h).  The LDS sort is this kernel's own: up to 2,048 keys at
+//       every distance, not the 64-key wave stage of wave_sort64.
+//   fpn_nms_mask_kernel   chip-wide 64x64 column-form IoU tiles of every (image, level)
+//       (tile_rows16 / tile_word, nms_iou.h).
 //   fpn_sweep_kernel      one workgroup per (image, level): greedy sweep in rank order
 //       with the ballot fixed point, stopping at post kept boxes.
 //   fpn_merge_kernel      one workgroup per image: rank of every kept box among the at
@@ -19,6 +22,7 @@
 #include "common.h"
 #include "elem16.h"
 #include "nms_iou.h"
+#include "radix_select.h"
 
 namespace frcnn {
 namespace {
@@ -71,43 +75,11 @@ FpnWs fpn_carve(void* ws, int N, int L, int cap) {
 }
 
 struct FpnSelShared {
-    unsigned digit, before, bucket, ccount;
+    RadixBin bin;
+    unsigned ccount;
     unsigned wsum[16];
     unsigned vsum[2][16];
 };
-
-// Block-wide: the bin d with cum(bins < d) < need <= cum(bins <= d) (1024 threads, <= 4096 bins).
-__device__ __forceinline__ void fpn_hist_find(const unsigned* hist, int nbins, unsigned need, FpnSelShared& sh) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    unsigned h[4], loc = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int bi = 4 * tid + q;
-        h[q] = bi < nbins ? hist[bi] : 0u;
-        loc += h[q];
-    }
-    unsigned incl = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) sh.wsum[wid] = incl;
-    __syncthreads();
-    unsigned before = incl - loc;
-    for (int w = 0; w < wid; ++w) before += sh.wsum[w];
-    if (before < need && before + loc >= need) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (before < need && before + h[q] >= need) {
-                sh.digit = 4 * tid + q;
-                sh.before = before;
-                sh.bucket = h[q];
-            }
-            before += h[q];
-        }
-    }
-    __syncthreads();
-}
 
 // Key of the logit at memory offset m = k * HW + cell of one image's [K, H, W] map:
 // anchor a = cell * K + k in the low word.
@@ -154,12 +126,12 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_select_decode_kernel(FpnLevel
                 if ((key & hm) == prefix) atomicAdd(&hist[static_cast<unsigned>(key >> shift) & (nbins - 1)], 1u);
             }
             __syncthreads();
-            fpn_hist_find(hist, nbins, need, sh);
-            need -= sh.before;
-            prefix |= static_cast<uint64_t>(sh.digit) << shift;
+            hist_find(hist, nbins, need, sh.bin, sh.wsum);
+            need -= sh.bin.before;
+            prefix |= static_cast<uint64_t>(sh.bin.digit) << shift;
             hm = ~0ull << shift;
             T = prefix | ((1ull << shift) - 1ull);
-            const bool whole = sh.bucket == need;  // every key of the bucket is selected
+            const bool whole = sh.bin.bucket == need;  // every key of the bucket is selected
             __syncthreads();                       // sh.* consumed before the next pass rewrites them
             if (whole) break;
         }
@@ -264,7 +236,7 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_select_decode_kernel(FpnLevel
 }
 
 // Tile (row block blockIdx.x, column block blockIdx.y) of slot blockIdx.z; 256 threads:
-// lane = column, wave w tests rows [16w, 16w+16), the four partial words are OR-ed in LDS.
+// lane = column, the rows split over the four waves (tile_rows16 / tile_word).
 __global__ __launch_bounds__(256) void fpn_nms_mask_kernel(FpnWs ws, int cap, int Wc, NmsThr thr) {
     const int rb = blockIdx.x, cb = blockIdx.y;
     if (rb > cb) return;
@@ -288,17 +260,8 @@ __global__ __launch_bounds__(256) void fpn_nms_mask_kernel(FpnWs ws, int cap, in
     const float aj = box_area(bj);
     __syncthreads();
     const int iend = jv ? min(min(64, V - i0), j - i0) : 0;  // rows before column j
-    uint64_t bits = 0;
-    if (!thr.never) {
-        const int r0 = wid * 16;
-#pragma unroll 4
-        for (int ii = r0; ii < r0 + 16; ++ii)
-            if (ii < iend && iou_over(rbox[ii], rarea[ii], bj, aj, thr)) bits |= 1ull << ii;
-    }
-    part[wid][lane] = bits;
-    __syncthreads();
-    if (wid == 0 && jv)
-        ws.mask[((slot * Wc + cb) * Wc + rb) * 64 + lane] = part[0][lane] | part[1][lane] | part[2][lane] | part[3][lane];
+    const uint64_t word = tile_word(part, wid, lane, tile_rows16(rbox, rarea, wid, iend, ~0ull, bj, aj, thr));
+    if (wid == 0 && jv) ws.mask[((slot * Wc + cb) * Wc + rb) * 64 + lane] = word;
 }
 
 // Greedy sweep of one (image, level) in rank order.  Thread t owns columns t and t + 1024
@@ -348,8 +311,7 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_sweep_kernel(FpnWs ws, int ca
                 if (Kn == Kb) break;
                 Kb = Kn;
             }
-            const int room = post - kcount;
-            while (__popcll(Kb) > room) Kb &= ~(1ull << (63 - __clzll(Kb)));  // keep the first `room`
+            Kb = first_bits(Kb, post - kcount);
             if ((Kb >> lane) & 1ull) {
                 const size_t at = slot * cap + kcount + __popcll(Kb & lanemask_lt());  // kept <= V <= cap
                 ws.kkey[at] = q ? key[1] : key[0];
@@ -396,19 +358,9 @@ __global__ __launch_bounds__(kFpnThreads) void fpn_merge_kernel(FpnWs ws, int L,
             int rank = p;
             for (int o = 0; o < L; ++o) {
                 if (o == l) continue;
-                const uint32_t* s = skeys + o * cap;
-                int lo = 0, len = s_cnt[o];
-                while (len > 0) {  // # of keys before ke: <= in a lower level, < in a higher one
-                    const int h = len >> 1;
-                    const uint32_t v = s[lo + h];
-                    if (o < l ? v <= ke : v < ke) {
-                        lo += h + 1;
-                        len -= h + 1;
-                    } else {
-                        len = h;
-                    }
-                }
-                rank += lo;
+                // # of keys before ke: <= in a lower level (ke + 1 does not wrap: keys stay below
+                // 0xFFFFFFFF), < in a higher one
+                rank += count_before(skeys + o * cap, s_cnt[o], o < l ? ke + 1 : ke);
             }
             if (rank < post) {
                 const size_t src = slot * cap + min(static_cast<unsigned>(ws.kslot[slot * cap + p]), cap - 1u);

@@ -69,13 +69,12 @@ __device__ __forceinline__ int read_label(const void* labels, int64_t r, int C) 
 __device__ __forceinline__ void block_sum(double& a, double& b, int& i0, int& i1, int& i2) {
     __shared__ double sd[2][kLossThreads / kWave];
     __shared__ int si[3][kLossThreads / kWave];
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_down(a, o, 64);
-        b += __shfl_down(b, o, 64);
-        i0 += __shfl_down(i0, o, 64);
-        i1 += __shfl_down(i1, o, 64);
-        i2 += __shfl_down(i2, o, 64);
-    }
+    // only lane 0's sums are used: there the butterfly adds the pairs of a shfl_down tree, in its order
+    a = wave_reduce(a, op_add{});
+    b = wave_reduce(b, op_add{});
+    i0 = wave_reduce(i0, op_add{});
+    i1 = wave_reduce(i1, op_add{});
+    i2 = wave_reduce(i2, op_add{});
     const int w = threadIdx.x / kWave;
     if (lane_id() == 0) {
         sd[0][w] = a, sd[1][w] = b;

@@ -1,5 +1,9 @@
 // torchvision's NMS suppression test, shared by the proposal layer / nms op
-// (proposal.hip) and the per-class detection NMS (detect.hip).
+// (proposal.hip), the FPN proposal layer (fpn_proposal.hip) and the per-class
+// detection NMS (detect.hip); and what the column-form NMS of the two proposal
+// units is made of: the 64x64 IoU tile and first_bits.  The ballot fixed point
+// that resolves a block stays written out in the three sweeps: the plan cases
+// (tests/propose_plan_cases.py) read its loops from proposal.hip's text.
 #pragma once
 
 #include <cfloat>
@@ -69,6 +73,38 @@ __device__ __forceinline__ float box_area(float4 b) {
     float dx = b.z - b.x;
     float dy = b.w - b.y;
     return dx * dy;
+}
+
+// ---- the column-form 64x64 IoU tile (proposal.hip's stage and first-chunk tiles,
+// fpn_proposal.hip's): 256 threads, lane = column, the tile's 64 row boxes and areas
+// staged in LDS.  Wave wid tests rows [16 wid, 16 wid + 16): bit ii of the result =
+// row ii, below iend and set in `rows`, suppresses this lane's column (bj, aj).
+__device__ __forceinline__ uint64_t tile_rows16(const float4* rbox, const float* rarea, int wid, int iend,
+                                                uint64_t rows, float4 bj, float aj, const NmsThr& thr) {
+    uint64_t bits = 0;
+    if (!thr.never) {
+        const int r0 = wid * 16;
+#pragma unroll 4
+        for (int ii = r0; ii < r0 + 16; ++ii)
+            if (ii < iend && ((rows >> ii) & 1ull) && iou_over(rbox[ii], rarea[ii], bj, aj, thr))
+                bits |= 1ull << ii;
+    }
+    return bits;
+}
+
+// The four waves' partial words OR-ed through LDS: the column's whole word.  One
+// barrier; part[] must stay as it is until the caller's next one.  The callers use
+// the word in wave 0 only, where the compiler then keeps the reads.
+__device__ __forceinline__ uint64_t tile_word(uint64_t (&part)[4][64], int wid, int lane, uint64_t bits) {
+    part[wid][lane] = bits;
+    __syncthreads();
+    return part[0][lane] | part[1][lane] | part[2][lane] | part[3][lane];
+}
+
+// The first `room` set bits of K.
+__device__ __forceinline__ uint64_t first_bits(uint64_t K, int room) {
+    while (__popcll(K) > room) K &= ~(1ull << (63 - __clzll(K)));
+    return K;
 }
 
 }  // namespace frcnn

@@ -15,6 +15,9 @@
 //       (nets/rpn.py:75-77).
 // Ties in score are ordered by ascending anchor index (documented deviation:
 // the reference's CPU argsort is unstable under ties).
+// Shared with fpn_proposal.hip, each in one place: the 64x64 column-form tile
+// (tile_rows16, tile_word) and first_bits in nms_iou.h; hist_find and wave_sort64 in radix_select.h; the
+// wave reduction / scan and count_before in common.h.
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -22,6 +25,7 @@
 
 #include "common.h"
 #include "nms_iou.h"
+#include "radix_select.h"
 
 namespace frcnn {
 
@@ -90,21 +94,6 @@ __device__ __forceinline__ uint64_t unique_key(uint64_t k, int a) {
     return k == kInvalidKey ? ((~0ull << 32) | static_cast<uint32_t>(a)) : k;
 }
 
-// # of keys < k in the sorted run s[0, len)
-__device__ __forceinline__ int lower_bound_u64(const uint64_t* s, int len, uint64_t k) {
-    int lo = 0, n = len;
-    while (n > 0) {
-        const int h = n >> 1;
-        if (s[lo + h] < k) {
-            lo += h + 1;
-            n -= h + 1;
-        } else {
-            n = h;
-        }
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(1024) void run_sort_kernel(const uint64_t* __restrict__ keys_all, int A, int nr,
                                                         uint64_t* __restrict__ runs_all, int* __restrict__ vcount) {
     FRCNN_CHAIN_PRIO();
@@ -118,22 +107,13 @@ __global__ __launch_bounds__(1024) void run_sort_kernel(const uint64_t* __restri
     uint64_t key = tid < len ? unique_key(raw, base + tid) : ~0ull;
     const uint64_t vb = __ballot(tid < len && raw != kInvalidKey);
     if (lane == 0) s_v[wid] = __popcll(vb);
-    for (int kk = 2; kk <= 64; kk <<= 1) {  // bitonic sort of the wave's 64 keys
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            const uint64_t other = __shfl_xor(key, j, 64);
-            const bool asc = (lane & kk) == 0;
-            const bool lower = (lane & j) == 0;
-            const uint64_t mn = other < key ? other : key;
-            const uint64_t mx = other < key ? key : other;
-            key = (lower == asc) ? mn : mx;
-        }
-    }
+    key = wave_sort64(key);
     s[tid] = key;
     __syncthreads();
     int rank = lane;
 #pragma unroll 1
     for (int w = 0; w < 16; ++w)
-        if (w != wid) rank += lower_bound_u64(s + 64 * w, 64, key);
+        if (w != wid) rank += count_before(s + 64 * w, 64, key);
     if (tid == 0) {
         int v = 0;
         for (int w = 0; w < 16; ++w) v += s_v[w];
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(1024) void merge_rank_kernel(const uint64_t* __rest
     __syncthreads();
     if (tid < leni)
         part[(static_cast<size_t>(n) * nr + j) * nr * kRun + i * kRun + tid] =
-            lower_bound_u64(s, lenj, runs[i * kRun + tid]);
+            count_before(s, lenj, runs[i * kRun + tid]);
 }
 
 // Per-image state of the staged NMS (carried from one stage launch to the next).
@@ -240,8 +220,10 @@ __device__ __forceinline__ void stage_tile(int t, int cb0, int& rb, int& cb) {
 // sweep turns a kept-row set into removed columns with one ballot per tile.
 // 256 threads per tile: lane = column, wave w tests rows [16w, 16w+16) of the
 // row block (4 independent waves per tile keep the SIMDs busy), the four
-// partial words are OR-ed in LDS.  The grid is capped (workgroups stride over
-// the stage's tiles), so a stage of a finished image costs one short launch.
+// partial words are OR-ed in LDS (tile_rows16 / tile_word, nms_iou.h; this
+// kernel's own: the kept-row filter K and prehit).  The grid is capped
+// (workgroups stride over the stage's tiles), so a stage of a finished image
+// costs one short launch.
 constexpr int kMaskGrid = 2048;
 
 __global__ __launch_bounds__(256) void nms_mask_stage_kernel(const float4* __restrict__ sbox_all, int pre,
@@ -286,18 +268,8 @@ __global__ __launch_bounds__(256) void nms_mask_stage_kernel(const float4* __res
         int iend = min(64, P - i0);
         if (rb == cb) iend = min(iend, lane);  // rows before the column
         if (!jv) iend = 0;
-        uint64_t bits = 0;
-        if (!thr.never) {
-            const int r0 = wid * 16;
-#pragma unroll 4
-            for (int ii = r0; ii < r0 + 16; ++ii)
-                if (ii < iend && ((K >> ii) & 1ull) && iou_over(rbox[ii], rarea[ii], bj, aj, thr))
-                    bits |= 1ull << ii;
-        }
-        part[wid][lane] = bits;
-        __syncthreads();
+        const uint64_t word = tile_word(part, wid, lane, tile_rows16(rbox, rarea, wid, iend, K, bj, aj, thr));
         if (wid == 0) {
-            const uint64_t word = part[0][lane] | part[1][lane] | part[2][lane] | part[3][lane];
             if (settled) {
                 const uint64_t h = __ballot(jv && word != 0ull);
                 if (lane == 0 && h) atomicOr(reinterpret_cast<unsigned long long*>(prehit) +
@@ -378,8 +350,7 @@ __global__ __launch_bounds__(1024) void nms_sweep_stage_kernel(
                     if (Kn == K) break;
                     K = Kn;
                 }
-                const int room = post - count;
-                while (__popcll(K) > room) K &= ~(1ull << (63 - __clzll(K)));  // keep the first `room`
+                K = first_bits(K, post - count);
                 if ((K >> lane) & 1ull) {
                     const int slot_i = count + __popcll(K & lanemask_lt());
                     if (OUT_MODE == 0) {
@@ -425,8 +396,8 @@ __global__ __launch_bounds__(1024) void nms_sweep_stage_kernel(
 //   * the image's score keys live in registers (KPT per lane, anchor index
 //     implied by the slot: a = tid + k*1024);
 //   * the next CHUNK(=1024) candidates in rank order are found with an exact
-//     radix select (12/12/8-bit digits, LDS histograms), compacted into LDS and
-//     bitonic-sorted (shuffles below 64, LDS above);
+//     radix select (12/12/8-bit digits, LDS histograms; hist_find), compacted
+//     into LDS and sorted (wave_sort64 per wave, then ranks over the wave runs);
 //   * NMS is lazy: each block of 64 sorted candidates is tested only against
 //     the boxes kept so far (16 waves split the kept list) and against itself
 //     (64x64 tile), then resolved by a wave with a fixed-point iteration
@@ -437,7 +408,7 @@ constexpr int kHistBins = 4096;
 constexpr int kFusedMaxA = 24 * 1024;  // keys held in registers: <= 24 per lane
 
 struct FusedShared {
-    unsigned digit, before, bucket;
+    RadixBin bin;
     unsigned ccount;
     int kcount;
     unsigned wsum[16];
@@ -445,40 +416,6 @@ struct FusedShared {
     uint64_t diag[64];
     uint64_t keptw[16];
 };
-
-// Block-wide: find the bin d with cum(bins < d) < need <= cum(bins <= d).
-__device__ __forceinline__ void hist_find(const unsigned* hist, int nbins, unsigned need,
-                                          FusedShared& sh) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    unsigned h[4], loc = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int bi = 4 * tid + q;
-        h[q] = bi < nbins ? hist[bi] : 0u;
-        loc += h[q];
-    }
-    unsigned incl = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) sh.wsum[wid] = incl;
-    __syncthreads();
-    unsigned before = incl - loc;
-    for (int w = 0; w < wid; ++w) before += sh.wsum[w];
-    if (before < need && before + loc >= need) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (before < need && before + h[q] >= need) {
-                sh.digit = 4 * tid + q;
-                sh.before = before;
-                sh.bucket = h[q];
-            }
-            before += h[q];
-        }
-    }
-    __syncthreads();
-}
 
 // r-th smallest (1-based) valid key64 = (score_key << 32 | anchor index).
 template <int KPT>
@@ -506,12 +443,12 @@ __device__ uint64_t select_rank(const uint32_t (&sk)[KPT], int A, unsigned r, un
             }
         }
         __syncthreads();
-        hist_find(hist, nbins, need, sh);
-        const unsigned d = sh.digit;
-        need -= sh.before;
+        hist_find(hist, nbins, need, sh.bin, sh.wsum);
+        const unsigned d = sh.bin.digit;
+        need -= sh.bin.before;
         prefix |= static_cast<uint64_t>(d) << shift;
         done += width;
-        const bool whole = sh.bucket == need;
+        const bool whole = sh.bin.bucket == need;
         __syncthreads();  // sh.* consumed before the next pass rewrites them
         if (whole) return prefix | ((1ull << shift) - 1ull);
     }
@@ -540,9 +477,7 @@ struct HybWs {
 };
 constexpr int kChunkBlocks = kChunk / 64;                           // 16
 
-// 256 threads per tile: lane = column, wave w tests rows [16w, 16w+16) of the
-// row block (4 waves per tile keep the SIMDs busy; the tests are independent),
-// the four partial words are OR-ed in LDS.
+// The tile of nms_mask_stage_kernel (tile_rows16 / tile_word), every row tested.
 __global__ __launch_bounds__(256) void chunk_colmask_kernel(const float4* __restrict__ cbox_all,
                                                             const int* __restrict__ cc_all, NmsThr thr,
                                                             uint64_t* __restrict__ colT, int nbt) {
@@ -570,18 +505,8 @@ __global__ __launch_bounds__(256) void chunk_colmask_kernel(const float4* __rest
     const float aj = box_area(bj);
     __syncthreads();
     const int iend = jv ? min(min(64, cc - i0), j - i0) : 0;  // rows before column j
-    uint64_t bits = 0;
-    if (!thr.never) {
-        const int r0 = wid * 16;
-#pragma unroll 4
-        for (int ii = r0; ii < r0 + 16; ++ii)
-            if (ii < iend && iou_over(rbox[ii], rarea[ii], bj, aj, thr)) bits |= 1ull << ii;
-    }
-    part[wid][lane] = bits;
-    __syncthreads();
-    if (wid == 0 && jv)
-        colT[(static_cast<size_t>(n) * kChunk + j) * kChunkBlocks + rb] =
-            part[0][lane] | part[1][lane] | part[2][lane] | part[3][lane];
+    const uint64_t word = tile_word(part, wid, lane, tile_rows16(rbox, rarea, wid, iend, ~0ull, bj, aj, thr));
+    if (wid == 0 && jv) colT[(static_cast<size_t>(n) * kChunk + j) * kChunkBlocks + rb] = word;
 }
 
 // Greedy NMS over the first chunk's rows [0, cc) from this image's colT.
@@ -589,7 +514,8 @@ __global__ __launch_bounds__(256) void chunk_colmask_kernel(const float4* __rest
 // order, block b by wave b: avail = its columns not hit by a kept row of an
 // earlier block, then the fixed point K <- avail & ~{j : diag_j & K != 0}
 // (unique, = the greedy result); the later waves fold block b's kept set into
-// their hit flags.  Kept boxes go to kbox/karea and the outputs, at most post.
+// their hit flags.  Kept boxes go to kbox/karea and the
+// outputs, at most post.
 __device__ int chunk_sweep(const uint64_t* __restrict__ colT, int cc, int post, const float4* cbox,
                            const float* carea, const uint64_t* ckey, float4* kbox, float* karea,
                            float4* orois, int32_t* oidx, FusedShared& sh) {
@@ -615,8 +541,7 @@ __device__ int chunk_sweep(const uint64_t* __restrict__ colT, int cc, int post, 
                 if (Kn == K) break;
                 K = Kn;
             }
-            const int room = post - kcount;
-            while (__popcll(K) > room) K &= ~(1ull << (63 - __clzll(K)));  // keep the first `room`
+            K = first_bits(K, post - kcount);
             if ((K >> lane) & 1ull) {
                 const int slot = kcount + __popcll(K & lanemask_lt());
                 const float4 bx = cbox[j];
@@ -718,7 +643,7 @@ __global__ __launch_bounds__(1024) void propose_fused_kernel(
             nv += sk[k] != 0xFFFFFFFFu;
         }
         if (MODE != 2) {
-            nv = wave_sum_u32(nv);
+            nv = wave_reduce(nv, op_add{});
             if (lane == 0) sh.wsum[wid] = nv;
             if (tid == 0) sh.kcount = 0;
             __syncthreads();
@@ -753,17 +678,7 @@ __global__ __launch_bounds__(1024) void propose_fused_kernel(
         // nrun waves that hold keys search (the other runs are all padding).
         const int nrun = (cc + 63) >> 6;
         const bool inrun = wid < nrun;  // wave-uniform
-        uint64_t key = tid < cc ? ckey[tid] : kInvalidKey;
-        for (int kk = 2; kk <= 64; kk <<= 1) {
-            for (int j = kk >> 1; j > 0; j >>= 1) {
-                const uint64_t other = __shfl_xor(key, j, 64);
-                const bool asc = (lane & kk) == 0;
-                const bool lower = (lane & j) == 0;
-                const uint64_t mn = other < key ? other : key;
-                const uint64_t mx = other < key ? key : other;
-                key = (lower == asc) ? mn : mx;
-            }
-        }
+        uint64_t key = wave_sort64(tid < cc ? ckey[tid] : kInvalidKey);
         __syncthreads();  // the reads of ckey above are done
         ckey[tid] = key;
         __syncthreads();
@@ -845,13 +760,12 @@ __global__ __launch_bounds__(1024) void propose_fused_kernel(
                 uint64_t K = avail;
 #pragma unroll 1
                 for (int it = 0; it < 65; ++it) {  // fixed point (<= 64 iterations)
-                    const uint64_t rb = wave_or_u64(((K >> lane) & 1ull) ? Dl : 0ull);
+                    const uint64_t rb = wave_reduce(((K >> lane) & 1ull) ? Dl : 0ull, op_or{});
                     const uint64_t Kn = avail & ~rb;
                     if (Kn == K) break;
                     K = Kn;
                 }
-                int room = post - kcount;
-                while (__popcll(K) > room) K &= ~(1ull << (63 - __clzll(K)));  // keep the first `room`
+                K = first_bits(K, post - kcount);
                 if ((K >> lane) & 1ull) {
                     const int slot = kcount + __popcll(K & lanemask_lt());
                     kbox[slot] = bj;

@@ -246,12 +246,7 @@ __global__ __launch_bounds__(1024) void at_label_kernel(
         cn += l == 0;
     }
     long long both = static_cast<long long>(cp) | (static_cast<long long>(cn) << 32);  // (no carries: < 2^31 each)
-    long long inc = both;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += u;
-    }
+    const long long inc = wave_scan_incl(both, op_add{});
     __shared__ long long s_wt[16];
     if (lane == 63) s_wt[wid] = inc;
     __syncthreads();
@@ -1080,21 +1075,11 @@ struct DrawBufs {
     uint32_t* tw;   // the words tempered, from the draws' first: word q of the draws is tw[q]
 };
 
-template <class T>
-__device__ __forceinline__ T wave_incl_scan(T v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
 // Inclusive scan of one value per thread over a 1024-thread block (sh: 16 slots).
 template <class T>
 __device__ T block_incl_scan(T v, T* sh, T& tot) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    v = wave_incl_scan(v);
+    v = wave_scan_incl(v, op_add{});
     if (lane == 63) sh[wid] = v;
     __syncthreads();
     T pre = 0, all = 0;
