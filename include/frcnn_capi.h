@@ -772,6 +772,12 @@ int frcnn_preprocess(int N, const uint8_t* pixels, int64_t pixels_bytes, const i
                      const int32_t* hw, int max_h, int max_w, int out_h, int out_w,
                      const float* mean, const float* std, float* out, int32_t* status,
                      void* workspace, size_t ws_bytes, void* stream);
+/* The launch plan frcnn_preprocess takes for these host bounds (host only, no
+ * HIP call; the launch reads the same function): plan = { TH (tile height; the
+ * tile is TH x 64 outputs), lds_rows, lds_cols (the staged source footprint's
+ * bound), max_taps (2 + 2r of the wider axis), lds_bytes, grid_x, grid_y,
+ * grid_z }.  Same argument checks as frcnn_preprocess. */
+int frcnn_preprocess_plan(int N, int max_h, int max_w, int out_h, int out_w, int32_t plan[8]);
 
 /* The boxes' rescale that goes with it (utils/data_loader.py:66-69), fp64:
  * boxes [N,G,4] as [ymin, xmin, ymax, xmax]; columns 0, 2 are b / h * out_h,

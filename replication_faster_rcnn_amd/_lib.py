@@ -122,6 +122,7 @@ SIGNATURES = {
     "frcnn_losses_bwd_t": (I32, [I32, I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),
     "frcnn_preprocess_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
     "frcnn_preprocess": (I32, [I32, P, I64, P, P, I32, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "frcnn_preprocess_plan": (I32, [I32, I32, I32, I32, I32, P]),
     "frcnn_rescale_boxes": (I32, [I32, I32, P, P, I32, I32, P, P]),
 }
 
@@ -336,6 +337,19 @@ def roi_align_multi_kernel(which: str, n_levels, R, N, C, PH=7, PW=7, sampling_r
     check(fn(dtype_code(dtype), int(n_levels), int(R), int(N), int(C), int(PH), int(PW), int(sampling_ratio), buf, 160),
           f"roi_align_multi_{which}_kernel")
     return buf.value.decode()
+
+
+PREPROCESS_PLAN_FIELDS = ("TH", "lds_rows", "lds_cols", "max_taps", "lds_bytes", "grid_x", "grid_y", "grid_z")
+
+
+def preprocess_plan(N, max_hw, out_hw) -> dict:
+    """frcnn_preprocess_plan: the tile height, footprint bounds, LDS bytes and grid that
+    ``frcnn_preprocess`` launches with for these host bounds, by PREPROCESS_PLAN_FIELDS.  Host only."""
+    lib = load(require_gpu=False)
+    plan = (ctypes.c_int32 * 8)()
+    check(lib.frcnn_preprocess_plan(int(N), int(max_hw[0]), int(max_hw[1]), int(out_hw[0]), int(out_hw[1]), plan),
+          "preprocess_plan")
+    return dict(zip(PREPROCESS_PLAN_FIELDS, plan))
 
 
 def set_path(op: str, path) -> None:

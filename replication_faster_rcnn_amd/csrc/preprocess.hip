@@ -290,6 +290,29 @@ const char* prep_args_error(int N, int max_h, int max_w, int out_h, int out_w) {
     return nullptr;
 }
 
+// The launch plan of frcnn_preprocess, from the host bounds alone: the tallest tile whose worst
+// footprint fits the LDS budget, that footprint, the tap rows' width and the grid.  The launch and
+// frcnn_preprocess_plan both read it from here.
+struct PrepPlan {
+    int TH, rows, cols, max_taps;
+    PrepLds L;
+    dim3 grid;
+};
+
+PrepPlan prep_plan(int N, int max_h, int max_w, int out_h, int out_w) {
+    PrepPlan p;
+    p.TH = kPrepMaxTH;
+    p.cols = span_bound(kPrepTW, max_w, out_w);
+    p.max_taps = std::max(span_bound(1, max_h, out_h), span_bound(1, max_w, out_w));  // 2 + 2r
+    for (;; p.TH /= 2) {
+        p.rows = span_bound(p.TH, max_h, out_h);
+        p.L = prep_lds(p.rows, p.cols, p.max_taps);
+        if (p.L.total <= kPrepLdsBudget || p.TH == 1) break;
+    }
+    p.grid = dim3((out_w + kPrepTW - 1) / kPrepTW, (out_h + p.TH - 1) / p.TH, N);
+    return p;
+}
+
 }  // namespace
 }  // namespace frcnn
 
@@ -298,6 +321,23 @@ using namespace frcnn;
 extern "C" size_t frcnn_preprocess_workspace_size(int N, int max_h, int max_w, int out_h, int out_w) {
     if (prep_args_error(N, max_h, max_w, out_h, out_w)) return 0;
     return 256;  // nothing is kept between launches: one nominal block, so that 0 still means "rejected"
+}
+
+extern "C" int frcnn_preprocess_plan(int N, int max_h, int max_w, int out_h, int out_w, int32_t plan[8]) {
+    if (const char* e = prep_args_error(N, max_h, max_w, out_h, out_w)) {
+        set_error("frcnn_preprocess_plan: %s (N=%d, max_h=%d, max_w=%d, out_h=%d, out_w=%d)", e, N, max_h, max_w,
+                  out_h, out_w);
+        return FRCNN_EINVAL;
+    }
+    FRCNN_REQUIRE(plan, "frcnn_preprocess_plan: null plan");
+    const PrepPlan p = prep_plan(N, max_h, max_w, out_h, out_w);
+    FRCNN_REQUIRE(p.L.total <= kPrepLdsBudget, "frcnn_preprocess_plan: internal: a %d x %d footprint needs %zu B of LDS",
+                  p.rows, p.cols, p.L.total);
+    const int32_t v[8] = {p.TH, p.rows, p.cols, p.max_taps, static_cast<int32_t>(p.L.total),
+                          static_cast<int32_t>(p.grid.x), static_cast<int32_t>(p.grid.y),
+                          static_cast<int32_t>(p.grid.z)};
+    std::copy(v, v + 8, plan);
+    return FRCNN_OK;
 }
 
 extern "C" int frcnn_preprocess(int N, const uint8_t* pixels, int64_t pixels_bytes, const int64_t* offset,
@@ -327,22 +367,12 @@ extern "C" int frcnn_preprocess(int N, const uint8_t* pixels, int64_t pixels_byt
         set_error("frcnn_preprocess: workspace of %zu B < %zu B", workspace ? ws_bytes : size_t{0}, need);
         return FRCNN_EWORKSPACE;
     }
-    // the tallest tile whose worst footprint (by the host's bounds) fits the LDS budget
-    int TH = kPrepMaxTH, rows = 0;
-    const int cols = span_bound(kPrepTW, max_w, out_w);
-    const int max_taps = std::max(span_bound(1, max_h, out_h), span_bound(1, max_w, out_w));  // 2 + 2r
-    PrepLds L;
-    for (;; TH /= 2) {
-        rows = span_bound(TH, max_h, out_h);
-        L = prep_lds(rows, cols, max_taps);
-        if (L.total <= kPrepLdsBudget || TH == 1) break;
-    }
-    FRCNN_REQUIRE(L.total <= kPrepLdsBudget, "frcnn_preprocess: internal: a %d x %d footprint needs %zu B of LDS", rows,
-                  cols, L.total);
-    const dim3 grid((out_w + kPrepTW - 1) / kPrepTW, (out_h + TH - 1) / TH, N);
-    preprocess_kernel<<<grid, kPrepThreads, L.total, as_stream(stream)>>>(pixels, pixels_bytes, offset, hw, max_h, max_w,
-                                                                         out_h, out_w, TH, rows, cols, L, k, out,
-                                                                         status);
+    const PrepPlan p = prep_plan(N, max_h, max_w, out_h, out_w);
+    FRCNN_REQUIRE(p.L.total <= kPrepLdsBudget, "frcnn_preprocess: internal: a %d x %d footprint needs %zu B of LDS",
+                  p.rows, p.cols, p.L.total);
+    preprocess_kernel<<<p.grid, kPrepThreads, p.L.total, as_stream(stream)>>>(pixels, pixels_bytes, offset, hw, max_h,
+                                                                           max_w, out_h, out_w, p.TH, p.rows, p.cols,
+                                                                           p.L, k, out, status);
     FRCNN_LAUNCH_CHECK("preprocess_kernel");
     return FRCNN_OK;
 }

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import preprocess_plan_cases as PC  # noqa: E402
 import preprocess_ref as R  # noqa: E402
 from replication_faster_rcnn_amd import data  # noqa: E402
 
@@ -36,10 +37,15 @@ def test_reference_matches_scipy(case):
 
 
 def test_case_table_covers_the_contract():
-    got = {(c[1], c[2]) for c in R.CASES}
+    got = {(c[1], c[2]) for c in R.CASES} | {(c.in_hw, c.out_hw) for c in PC.CASES}
     for pair in [((4, 5), (4, 5)), ((5, 7), (12, 12)), ((2, 3), (8, 8)), ((1, 1), (4, 4)), ((13, 9), (6, 12)),
                  ((20, 31), (6, 7)), ((64, 48), (37, 41)), ((24, 24), (6, 6)), ((4, 4), (1, 1)),
-                 ((3, 499), (4, 600)), ((375, 500), (600, 600))]:
+                 ((3, 499), (4, 600)), ((375, 500), (600, 600)),
+                 # the launch-plan cases (tests/preprocess_plan_cases.py)
+                 ((90, 200), (45, 100)), ((46, 161), (20, 70)), ((60, 60), (12, 12)), ((30, 650), (6, 130)),
+                 ((120, 40), (40, 100)), ((20, 300), (50, 100)), ((10, 96), (10, 64)), ((10, 98), (10, 65)),
+                 ((66, 20), (33, 16)), ((20, 20), (33, 16)), ((20, 12), (33, 16)), ((2, 40), (1, 20)),
+                 ((2, 2), (1, 1)), ((1, 130), (3, 65)), ((500, 375), (200, 150)), ((2, 16384), (1, 4096))]:
         assert pair in got, pair
     kinds = {c[3] for c in R.CASES}
     assert kinds == {"random", "checker", "zeros", "full"}
