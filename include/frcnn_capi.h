@@ -299,6 +299,25 @@ int frcnn_roi_align_fwd_kernel(int dtype, int64_t R, int N, int C, int H, int W,
                                int sampling_ratio, char* name, size_t len);
 int frcnn_roi_align_bwd_kernel(int dtype, int64_t R, int N, int C, int H, int W, int PH, int PW,
                                int sampling_ratio, char* name, size_t len);
+/* The launch plan of the two calls for this shape (host only, no HIP call; the
+ * launches read the same functions), and the constants behind it:
+ *   plan = { run (channels per forward thread, 8), tile (backward tile edge, 8),
+ *            stride (LDS words per pixel row, 65), waves (tiles per workgroup, 5),
+ *            stage_bins (a RoI's gradients are staged in LDS up to PH*PW = 49),
+ *            scan (sampling grids up to 16 points per axis are walked whole),
+ *            lane_samples (up to 64 samples per axis go one per lane),
+ *            fwd_threads, fwd_grid (workgroups of 256; both 0 where the forward
+ *            only clears `out`: N, H or W == 0),
+ *            tiles_x, tiles_y, cgroups (groups of 64 channels), units (tiles_x *
+ *            tiles_y * cgroups * N), blocks, idle (waves of the last workgroup
+ *            without a unit), lds_bytes, staged (PH*PW <= stage_bins) }.
+ * Same shape checks as the calls, the backward's "map too large" included. */
+int frcnn_roi_align_plan(int64_t R, int N, int C, int H, int W, int PH, int PW, int64_t plan[17]);
+/* The pyramid backward's: plan = { first[0..8] (level l owns the units [first[l],
+ * first[l + 1]); first[8] = units), cgroups, units, blocks, idle, staged }.  H, W:
+ * host arrays of n_levels entries. */
+int frcnn_roi_align_multi_plan(int n_levels, const int* H, const int* W, int N, int C, int PH, int PW,
+                               int64_t plan[14]);
 
 /* Multi-scale RoIAlign over a feature pyramid (torchvision.ops.MultiScaleRoIAlign's
  * pooling; DESIGN.md §3 "Multi-scale RoIAlign"): every RoI is pooled from the level

@@ -77,6 +77,8 @@ SIGNATURES = {
     "frcnn_roi_align_bwd_t": (I32, [I32, P, P, I64, I32, I32, I32, I32, I32, I32, F32, I32, I32, P, P, SZ, P]),
     "frcnn_roi_align_fwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_roi_align_bwd_kernel": (I32, [I32, I64, I32, I32, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_roi_align_plan": (I32, [I64, I32, I32, I32, I32, I32, I32, P]),
+    "frcnn_roi_align_multi_plan": (I32, [I32, P, P, I32, I32, I32, I32, P]),
     "frcnn_roi_align_multi_fwd_t": (I32, [I32, I32, P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, P, P, P, SZ, P]),
     "frcnn_roi_align_multi_bwd_t": (I32, [I32, I32, P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, P, P, SZ, P]),
     "frcnn_roi_align_multi_fwd_kernel": (I32, [I32, I32, I64, I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
@@ -337,6 +339,32 @@ def roi_align_multi_kernel(which: str, n_levels, R, N, C, PH=7, PW=7, sampling_r
     check(fn(dtype_code(dtype), int(n_levels), int(R), int(N), int(C), int(PH), int(PW), int(sampling_ratio), buf, 160),
           f"roi_align_multi_{which}_kernel")
     return buf.value.decode()
+
+
+ROI_ALIGN_PLAN_FIELDS = ("run", "tile", "stride", "waves", "stage_bins", "scan", "lane_samples", "fwd_threads",
+                         "fwd_grid", "tiles_x", "tiles_y", "cgroups", "units", "blocks", "idle", "lds_bytes", "staged")
+ROI_ALIGN_MULTI_PLAN_FIELDS = ("first", "cgroups", "units", "blocks", "idle", "staged")
+
+
+def roi_align_plan(R, N, C, H, W, PH=7, PW=7) -> dict:
+    """frcnn_roi_align_plan: the kernels' constants and the launch numbers of the RoIAlign
+    forward and backward for this shape, by ROI_ALIGN_PLAN_FIELDS.  Host only."""
+    lib = load(require_gpu=False)
+    plan = (ctypes.c_int64 * 17)()
+    check(lib.frcnn_roi_align_plan(int(R), int(N), int(C), int(H), int(W), int(PH), int(PW), plan), "roi_align_plan")
+    return dict(zip(ROI_ALIGN_PLAN_FIELDS, plan))
+
+
+def roi_align_multi_plan(sizes, N, C, PH=7, PW=7) -> dict:
+    """frcnn_roi_align_multi_plan for the levels' (H, W) ``sizes``: ``first`` (the nine unit
+    offsets; level l owns [first[l], first[l + 1])) and the launch numbers of the pyramid
+    backward, by ROI_ALIGN_MULTI_PLAN_FIELDS.  Host only."""
+    lib = load(require_gpu=False)
+    L = len(sizes)
+    H, W = (I32 * max(L, 1))(*[int(s[0]) for s in sizes]), (I32 * max(L, 1))(*[int(s[1]) for s in sizes])
+    plan = (ctypes.c_int64 * 14)()
+    check(lib.frcnn_roi_align_multi_plan(L, H, W, int(N), int(C), int(PH), int(PW), plan), "roi_align_multi_plan")
+    return dict(first=list(plan[:9]), **dict(zip(ROI_ALIGN_MULTI_PLAN_FIELDS[1:], plan[9:])))
 
 
 PREPROCESS_PLAN_FIELDS = ("TH", "lds_rows", "lds_cols", "max_taps", "lds_bytes", "grid_x", "grid_y", "grid_z")

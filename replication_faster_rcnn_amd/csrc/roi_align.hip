@@ -56,6 +56,7 @@ constexpr int kAlignStageBins = 49;        // backward: a RoI's gradients are st
 constexpr int kAlignMaxDim = 1 << 24;      // H, W must be exact in fp32
 constexpr int kAlignRun = 8;               // forward: channels per thread
 constexpr int kAlignMaxLevels = 8;         // pyramid: most levels in one call
+constexpr int kAlignLaneSamples = 64;      // backward: up to this many samples per axis go one per lane
 
 struct AlignGeom {
     float sh, sw, bh, bw, count;
@@ -419,8 +420,9 @@ __device__ __forceinline__ void align_bwd_tile(const typename E::raw* __restrict
                     if (!active) return 0.f;
                     return staged ? stage[lane * sstride + ph * PW + pw] : E::widen(gp[static_cast<size_t>(ph) * PW + pw]);
                 };
-                if (g.gh > 0 && g.gw > 0 && g.gh <= 64 && g.gw <= 64 && PH <= 64 && PW <= 64 && PH * g.gh <= 64 &&
-                    PW * g.gw <= 64) {
+                constexpr int kLane = kAlignLaneSamples;
+                if (g.gh > 0 && g.gw > 0 && g.gh <= kLane && g.gw <= kLane && PH <= kLane && PW <= kLane &&
+                    PH * g.gh <= kLane && PW * g.gw <= kLane) {
                     // Up to 64 samples per axis (every fixed sampling_ratio at 7 x 7 up to 9): lane l works out
                     // sample l of each axis once, the walk below reads the values lane by lane.
                     int tyl = 0, tyh = 0, txl = 0, txh = 0;
@@ -605,14 +607,64 @@ int align_check(const char* fn, int dtype, int64_t R, int N, int C, int H, int W
     return FRCNN_OK;
 }
 
+// The launch numbers of both directions, from the shape alone.  The launches below and
+// frcnn_roi_align_plan / frcnn_roi_align_multi_plan all read them from here.
+struct AlignFwdPlan {
+    int runs;             // runs of kAlignRun channels per bin
+    int64_t total, grid;  // threads, workgroups of 256
+};
+
+AlignFwdPlan align_fwd_plan(int64_t R, int C, int PH, int PW, bool levels_only_row) {
+    AlignFwdPlan p;
+    p.runs = (C + kAlignRun - 1) / kAlignRun;
+    if (levels_only_row && C == 0) p.runs = 1;  // pyramid, C == 0: one thread row, for `levels`
+    p.total = R * p.runs * PH * PW;
+    p.grid = (p.total + 255) / 256;
+    return p;
+}
+
+struct AlignBwdPlan {
+    int tiles_x, tiles_y, cgroups, idle;  // idle: waves of the last workgroup without a unit
+    int64_t tiles, units, blocks;
+    size_t lds;
+    bool staged;
+};
+
+constexpr size_t kAlignBwdLds =
+    sizeof(float) * kAlignWaves * (kAlignTile * kAlignTile * kAlignTileStride + 64 * kAlignStageBins);
+
+// One map's tile grid; `units` and what follows from it are the caller's (the pyramid sums levels).
+void align_tile_grid(int H, int W, AlignBwdPlan& p) {
+    p.tiles_x = (W + kAlignTile - 1) / kAlignTile;
+    p.tiles_y = (H + kAlignTile - 1) / kAlignTile;
+    p.tiles = static_cast<int64_t>(p.tiles_x) * p.tiles_y;
+}
+
+void align_units(int64_t units, int PH, int PW, AlignBwdPlan& p) {
+    p.units = units;
+    p.blocks = (units + kAlignWaves - 1) / kAlignWaves;
+    p.idle = static_cast<int>(p.blocks * kAlignWaves - units);
+    p.lds = kAlignBwdLds;
+    p.staged = static_cast<int64_t>(PH) * PW <= kAlignStageBins;
+}
+
+int align_bwd_plan(const char* fn, int N, int C, int H, int W, int PH, int PW, AlignBwdPlan& p) {
+    align_tile_grid(H, W, p);
+    p.cgroups = (C + 63) / 64;
+    align_units(p.tiles * p.cgroups * N, PH, PW, p);
+    FRCNN_REQUIRE(p.tiles <= 0x7fffffff && p.blocks <= 0x7fffffff, "%s: map too large (%lld tiles)", fn,
+                  static_cast<long long>(p.units));
+    return FRCNN_OK;
+}
+
 template <class E>
 int align_fwd_launch(const void* x, const float* rois, int64_t R, int N, int C, int H, int W, int PH, int PW,
                      float scale, int sampling_ratio, int aligned, void* out, hipStream_t st) {
     using raw = typename E::raw;
-    const int64_t total = R * ((C + kAlignRun - 1) / kAlignRun) * PH * PW;  // threads
-    const unsigned grid = static_cast<unsigned>((total + 255) / 256);
-    hipLaunchKernelGGL(roi_align_fwd_kernel<E>, dim3(grid), dim3(256), 0, st, static_cast<const raw*>(x), rois, total,
-                       N, C, H, W, PH, PW, scale, sampling_ratio, aligned, static_cast<raw*>(out));
+    const AlignFwdPlan p = align_fwd_plan(R, C, PH, PW, false);
+    hipLaunchKernelGGL(roi_align_fwd_kernel<E>, dim3(static_cast<unsigned>(p.grid)), dim3(256), 0, st,
+                       static_cast<const raw*>(x), rois, p.total, N, C, H, W, PH, PW, scale, sampling_ratio, aligned,
+                       static_cast<raw*>(out));
     return check_launch("roi_align_fwd_kernel");
 }
 
@@ -621,17 +673,12 @@ int align_bwd_launch(const void* grad, const float* rois, int R, int N, int C, i
                      float scale, int sampling_ratio, int aligned, void* grad_in, hipStream_t st) {
     using raw = typename E::raw;
     constexpr int T = kAlignTile;
-    const int tiles_x = (W + T - 1) / T, tiles_y = (H + T - 1) / T;
-    const int64_t tiles = static_cast<int64_t>(tiles_x) * tiles_y;
-    const int cgroups = (C + 63) / 64;
-    const int64_t units = tiles * cgroups * N;
-    const int64_t blocks = (units + kAlignWaves - 1) / kAlignWaves;
-    FRCNN_REQUIRE(tiles <= 0x7fffffff && blocks <= 0x7fffffff, "frcnn_roi_align_bwd_t: map too large (%lld tiles)",
-                  static_cast<long long>(units));
-    const size_t lds = sizeof(float) * kAlignWaves * (T * T * kAlignTileStride + 64 * kAlignStageBins);
-    hipLaunchKernelGGL((roi_align_bwd_tile_kernel<E, T>), dim3(static_cast<unsigned>(blocks)), dim3(64 * kAlignWaves),
-                       lds, st, static_cast<const raw*>(grad), rois, R, N, C, H, W, PH, PW, scale, sampling_ratio,
-                       aligned, tiles_x, static_cast<int>(tiles), cgroups, units, static_cast<raw*>(grad_in));
+    AlignBwdPlan p;
+    if (int rc = align_bwd_plan("frcnn_roi_align_bwd_t", N, C, H, W, PH, PW, p)) return rc;
+    hipLaunchKernelGGL((roi_align_bwd_tile_kernel<E, T>), dim3(static_cast<unsigned>(p.blocks)),
+                       dim3(64 * kAlignWaves), p.lds, st, static_cast<const raw*>(grad), rois, R, N, C, H, W, PH, PW,
+                       scale, sampling_ratio, aligned, p.tiles_x, static_cast<int>(p.tiles), p.cgroups, p.units,
+                       static_cast<raw*>(grad_in));
     return check_launch("roi_align_bwd_tile_kernel");
 }
 
@@ -667,12 +714,35 @@ template <class E>
 int align_multi_fwd_launch(const AlignLevels& lv, const float* rois, int64_t R, int N, int C, int PH, int PW,
                            int sampling_ratio, int aligned, void* out, int* levels, hipStream_t st) {
     using raw = typename E::raw;
-    const int runs = C > 0 ? (C + kAlignRun - 1) / kAlignRun : 1;  // C == 0: one thread row, for `levels`
-    const int64_t total = R * runs * PH * PW;                      // threads
-    const unsigned grid = static_cast<unsigned>((total + 255) / 256);
-    hipLaunchKernelGGL(roi_align_multi_fwd_kernel<E>, dim3(grid), dim3(256), 0, st, lv, rois, total, N, C, runs, PH,
-                       PW, sampling_ratio, aligned, static_cast<raw*>(out), levels);
+    const AlignFwdPlan p = align_fwd_plan(R, C, PH, PW, true);
+    hipLaunchKernelGGL(roi_align_multi_fwd_kernel<E>, dim3(static_cast<unsigned>(p.grid)), dim3(256), 0, st, lv, rois,
+                       p.total, N, C, p.runs, PH, PW, sampling_ratio, aligned, static_cast<raw*>(out), levels);
     return check_launch("roi_align_multi_fwd_kernel");
+}
+
+// The pyramid backward's tile space and launch numbers (level l owns [first[l], first[l + 1])).
+int align_multi_bwd_plan(const char* fn, int n_levels, const int* H, const int* W, int N, int C, int PH, int PW,
+                         AlignTilePlan& plan, AlignBwdPlan& p) {
+    std::memset(&plan, 0, sizeof(plan));
+    p.tiles_x = p.tiles_y = 0;
+    p.tiles = 0;
+    p.cgroups = (C + 63) / 64;
+    int64_t units = 0;
+    for (int l = 0; l < kAlignMaxLevels; ++l) {
+        plan.first[l] = units;
+        if (l >= n_levels) continue;
+        AlignBwdPlan g;
+        align_tile_grid(H[l], W[l], g);
+        FRCNN_REQUIRE(g.tiles <= 0x7fffffff, "%s: level %d too large (%lld tiles)", fn, l,
+                      static_cast<long long>(g.tiles));
+        plan.tiles_x[l] = g.tiles_x;
+        plan.tiles[l] = static_cast<int>(g.tiles);
+        units += g.tiles * p.cgroups * N;
+    }
+    plan.first[kAlignMaxLevels] = units;
+    align_units(units, PH, PW, p);
+    FRCNN_REQUIRE(p.blocks <= 0x7fffffff, "%s: maps too large (%lld tiles)", fn, static_cast<long long>(units));
+    return FRCNN_OK;
 }
 
 template <class E>
@@ -680,30 +750,13 @@ int align_multi_bwd_launch(const AlignLevels& lv, const void* grad, const float*
                            int PW, int sampling_ratio, int aligned, hipStream_t st) {
     using raw = typename E::raw;
     constexpr int T = kAlignTile;
-    const int cgroups = (C + 63) / 64;
     AlignTilePlan plan;
-    std::memset(&plan, 0, sizeof(plan));
-    int64_t units = 0;
-    for (int l = 0; l < kAlignMaxLevels; ++l) {
-        plan.first[l] = units;
-        if (l >= lv.n) continue;
-        const int tiles_x = (lv.W[l] + T - 1) / T, tiles_y = (lv.H[l] + T - 1) / T;
-        const int64_t tiles = static_cast<int64_t>(tiles_x) * tiles_y;
-        FRCNN_REQUIRE(tiles <= 0x7fffffff, "frcnn_roi_align_multi_bwd_t: level %d too large (%lld tiles)", l,
-                      static_cast<long long>(tiles));
-        plan.tiles_x[l] = tiles_x;
-        plan.tiles[l] = static_cast<int>(tiles);
-        units += tiles * cgroups * N;
-    }
-    plan.first[kAlignMaxLevels] = units;
-    if (units == 0) return FRCNN_OK;
-    const int64_t blocks = (units + kAlignWaves - 1) / kAlignWaves;
-    FRCNN_REQUIRE(blocks <= 0x7fffffff, "frcnn_roi_align_multi_bwd_t: maps too large (%lld tiles)",
-                  static_cast<long long>(units));
-    const size_t lds = sizeof(float) * kAlignWaves * (T * T * kAlignTileStride + 64 * kAlignStageBins);
-    hipLaunchKernelGGL((roi_align_multi_bwd_tile_kernel<E, T>), dim3(static_cast<unsigned>(blocks)),
-                       dim3(64 * kAlignWaves), lds, st, static_cast<const raw*>(grad), rois, R, N, C, PH, PW,
-                       sampling_ratio, aligned, cgroups, units, lv, plan);
+    AlignBwdPlan p;
+    if (int rc = align_multi_bwd_plan("frcnn_roi_align_multi_bwd_t", lv.n, lv.H, lv.W, N, C, PH, PW, plan, p)) return rc;
+    if (p.units == 0) return FRCNN_OK;
+    hipLaunchKernelGGL((roi_align_multi_bwd_tile_kernel<E, T>), dim3(static_cast<unsigned>(p.blocks)),
+                       dim3(64 * kAlignWaves), p.lds, st, static_cast<const raw*>(grad), rois, R, N, C, PH, PW,
+                       sampling_ratio, aligned, p.cgroups, p.units, lv, plan);
     return check_launch("roi_align_multi_bwd_tile_kernel");
 }
 
@@ -868,5 +921,44 @@ extern "C" int frcnn_roi_align_multi_bwd_kernel(int dtype, int n_levels, int64_t
     FRCNN_REQUIRE(name && len > 0, "%s: null name", fn);
     const int n = snprintf(name, len, "roi_align_multi_bwd_tile_kernel<%s, %d>", align_elem_name(dtype), kAlignTile);
     FRCNN_REQUIRE(n >= 0 && static_cast<size_t>(n) < len, "%s: name buffer of %zu bytes too small", fn, len);
+    return FRCNN_OK;
+}
+
+// ------------------------------------------------------------------ launch plans (host only)
+extern "C" int frcnn_roi_align_plan(int64_t R, int N, int C, int H, int W, int PH, int PW, int64_t plan[17]) {
+    const char* fn = "frcnn_roi_align_plan";
+    if (int rc = align_check(fn, FRCNN_F32, R, N, C, H, W, PH, PW, 0)) return rc;
+    FRCNN_REQUIRE(plan, "%s: null plan", fn);
+    const int64_t per_roi = static_cast<int64_t>(C) * PH * PW;
+    FRCNN_REQUIRE(per_roi == 0 || R <= (int64_t{1} << 38) / per_roi, "%s: output too large", fn);
+    AlignFwdPlan f = align_fwd_plan(R, C, PH, PW, false);
+    if (N == 0 || H == 0 || W == 0) f.total = f.grid = 0;  // no pixel to sample: a memset, no launch
+    AlignBwdPlan b;
+    if (int rc = align_bwd_plan(fn, N, C, H, W, PH, PW, b)) return rc;
+    const int64_t v[17] = {kAlignRun, kAlignTile, kAlignTileStride, kAlignWaves, kAlignStageBins, kAlignScan,
+                           kAlignLaneSamples, f.total, f.grid, b.tiles_x, b.tiles_y, b.cgroups, b.units, b.blocks,
+                           b.idle, static_cast<int64_t>(b.lds), b.staged ? 1 : 0};
+    for (int i = 0; i < 17; ++i) plan[i] = v[i];
+    return FRCNN_OK;
+}
+
+extern "C" int frcnn_roi_align_multi_plan(int n_levels, const int* H, const int* W, int N, int C, int PH, int PW,
+                                          int64_t plan[14]) {
+    const char* fn = "frcnn_roi_align_multi_plan";
+    FRCNN_REQUIRE(n_levels >= 1 && n_levels <= kAlignMaxLevels, "%s: n_levels %d is not in [1, %d]", fn, n_levels,
+                  kAlignMaxLevels);
+    FRCNN_REQUIRE(H && W, "%s: null %s", fn, !H ? "H" : "W");
+    FRCNN_REQUIRE(plan, "%s: null plan", fn);
+    for (int l = 0; l < n_levels; ++l)
+        if (int rc = align_check(fn, FRCNN_F32, 0, N, C, H[l], W[l], PH, PW, 0)) return rc;
+    AlignTilePlan t;
+    AlignBwdPlan b;
+    if (int rc = align_multi_bwd_plan(fn, n_levels, H, W, N, C, PH, PW, t, b)) return rc;
+    for (int l = 0; l <= kAlignMaxLevels; ++l) plan[l] = t.first[l];
+    plan[9] = b.cgroups;
+    plan[10] = b.units;
+    plan[11] = b.blocks;
+    plan[12] = b.idle;
+    plan[13] = b.staged ? 1 : 0;
     return FRCNN_OK;
 }

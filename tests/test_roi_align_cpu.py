@@ -14,7 +14,8 @@ F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "frcnn_capi.h")
 SYMBOLS = ["frcnn_roi_align_fwd_t", "frcnn_roi_align_bwd_t", "frcnn_roi_align_fwd_workspace_size",
-           "frcnn_roi_align_bwd_workspace_size", "frcnn_roi_align_fwd_kernel", "frcnn_roi_align_bwd_kernel"]
+           "frcnn_roi_align_bwd_workspace_size", "frcnn_roi_align_fwd_kernel", "frcnn_roi_align_bwd_kernel",
+           "frcnn_roi_align_plan", "frcnn_roi_align_multi_plan"]
 
 
 def _ramps():
