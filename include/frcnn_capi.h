@@ -416,6 +416,90 @@ int frcnn_propose_multi_t(int dtype, int n_levels, const void* const* objectness
 int frcnn_propose_multi_kernel(int dtype, int n_levels, int N, int K, const int* H, const int* W, int pre_nms,
                                int post_nms, char* name, size_t len);
 
+/* Pyramid RPN training targets: torchvision's assign_targets_to_anchors (box_iou + Matcher
+ * with set_low_quality_matches_), BalancedPositiveNegativeSampler and BoxCoder.encode with
+ * weights (1, 1, 1, 1) for a whole batch and pyramid (DESIGN.md §3 "Pyramid RPN training"):
+ * five launches, no host sync, no device allocation, no floating-point atomics; the same
+ * inputs (rng included) give the same bits on every call.
+ *   anchor_bases, H, W, stride_h, stride_w: HOST arrays of L entries as frcnn_propose_multi_t
+ *   takes them; anchor_bases[l] is a device pointer, fp32 [K,4], 16-byte aligned.  The global
+ *   anchor index is off_l + (y*W_l + x)*K + k, levels in the order given; A is the total.
+ *   gt_boxes fp32 [N,G,4] (x1, y1, x2, y2), 16-byte aligned; gt_count int32 [N], clamped to
+ *   [0, G]; rng int64 [2] = (seed, calls): device pointers.  rng is read on the device and the
+ *   last launch stores calls + 1.
+ * Matching, fp32, every operation rounded separately: area = (x2-x1)*(y2-y1), inter = the
+ * product of max(min(x2,x2') - max(x1,x1'), 0) and the same in y, iou = inter / ((area_gt +
+ * area_anchor) - inter), IEEE divide; inter == 0 gives 0 and a NaN quotient counts as 0.  A gt
+ * row below gt_count that is not finite or has x2 <= x1 or y2 <= y1 is absent (its index still
+ * counts).  Per anchor the largest IoU over the present rows, the lowest index on a tie;
+ * iou < (float)bg -> -1, iou < (float)fg -> -2, else the index.  With allow_low_quality_matches
+ * every anchor whose IoU with some present gt g equals the largest IoU any anchor has with g
+ * (compared as fp32; 0 == 0 counts) gets its own argmax back.  No present row: -1 everywhere.
+ * Sampling: positives are matches >= 0, negatives matches == -1; num_pos = min(P, (int)(B *
+ * positive_fraction)) (the double product truncated), num_neg = min(Ng, B - num_pos); chosen
+ * are those with the smallest (key, anchor index), key = word 0 of Philox4x32-10 with counter
+ * (anchor index, n, calls & 0xFFFFFFFF, calls >> 32) and key (seed & 0xFFFFFFFF, seed >> 32),
+ * all but its top key_bits bits cleared (32: the whole key; 0: every key ties; a test knob).
+ * Outputs, every element stored exactly once per call:
+ *   matches int32 [N,A]; sampled int32 [N,A] (1 sampled positive, 0 sampled negative, -1);
+ *   samples int32 [N,B]: the sampled positives in ascending index, then the negatives in
+ *   ascending index, then -1; n_pos, n_neg int32 [N]; reg_targets fp32 [N,B,4], 16-byte
+ *   aligned: for the positive rows w = x2-x1, cx = x1 + 0.5*w of anchor and matched gt,
+ *   (dx, dy, dw, dh) = ((gcx-cx)/w, (gcy-cy)/h, log(gw/w), log(gh/h)) with a correctly
+ *   rounded log; every other row is zero.
+ * Limits (FRCNN_EINVAL with a message before any launch, like NULLs, misaligned pointers and
+ * a short workspace): 1 <= L <= 8, 1 <= N <= 1024, 1 <= K <= 32, 1 <= G <= 256, H, W >= 1,
+ * K*H*W < 2^24 per level, (H-1)*stride_h and (W-1)*stride_w < 2^24, strides >= 1, A < 2^31,
+ * 1 <= batch_size_per_image <= 1024, positive_fraction in [0, 1], bg_iou_thresh <=
+ * fg_iou_thresh, key_bits in [0, 32].  The workspace is stream-ordered scratch, 256-byte
+ * aligned (about 4*N*A bytes: it keeps every anchor's key between the launches); nothing in it
+ * needs to be initialised. */
+size_t frcnn_rpn_targets_multi_workspace_size(int n_levels, int N, int K, const int* H, const int* W, int G,
+                                              int batch_size_per_image);
+int frcnn_rpn_targets_multi(int n_levels, const float* const* anchor_bases, const int* H, const int* W,
+                            const int* stride_h, const int* stride_w, int N, int K, const float* gt_boxes,
+                            const int32_t* gt_count, int G, int64_t* rng, int batch_size_per_image,
+                            double positive_fraction, double fg_iou_thresh, double bg_iou_thresh,
+                            int allow_low_quality_matches, int key_bits, int32_t* matches, int32_t* sampled,
+                            int32_t* samples, int32_t* n_pos, int32_t* n_neg, float* reg_targets, void* workspace,
+                            size_t ws_bytes, void* stream);
+/* The kernels a call of this shape launches, in order, with what of the plan the shape fixes:
+ * the workgroups per image of the chip-wide kernels (1024 anchors each) and the anchors of the
+ * last one; for the select kernel the number of boundary-bucket keys it sorts in LDS (lds=), the
+ * digits of the key its radix passes refine when a boundary bucket holds more than that (radix=8 |
+ * 8+12 | 8+12+12 by key_bits <= 8 | <= 20 | above; which of the two happens depends on the data) and
+ * the 4096-anchor steps of one of its sweeps over an image:
+ * "rpnt_init_kernel rpnt_gtmax_kernel[chunks=88,tail=1002] rpnt_label_kernel
+ *  rpnt_select_kernel[lds=4096,radix=8+12+12,steps=22] rpnt_finish_kernel". */
+int frcnn_rpn_targets_multi_kernel(int n_levels, int N, int K, const int* H, const int* W, int G,
+                                   int batch_size_per_image, int key_bits, char* name, size_t len);
+
+/* Pyramid RPN losses: torchvision's RegionProposalNetwork.compute_loss on the targets above,
+ * forward and backward.  objectness[l] `dtype` [N,K,H[l],W[l]], deltas[l] `dtype`
+ * [N,4K,H[l],W[l]] (channel 4k + c), read in place as frcnn_propose_multi_t reads them.
+ * Forward, over the S = sum(n_pos + n_neg) sample slots: per-element fp32, (max(x,0) - x*t) +
+ * log1p(exp(-|x|)) with correctly rounded exp / log1p against t = 1 (slot < n_pos) or 0, and
+ * for the positives' four coordinates z = |x - target|, z < (float)beta ? 0.5*z*z/beta :
+ * z - 0.5*beta; the terms are added in fp64 in a fixed order; loss[0] = objectness sum / S,
+ * loss[1] = box sum / S, each rounded once (S == 0: NaN); stats[0] = S, stats[1] = 0.
+ * Backward: dobjectness[l] / ddeltas[l] in `dtype`, every element stored exactly once: +0
+ * where sampled < 0 (and in ddeltas where sampled == 0), else (sigmoid(x) - t) * (*g_obj / S)
+ * and (z < beta ? (x - target)/beta : sign(x - target)) * (*g_box / S), fp32, rounded once at
+ * the store.  g_obj / g_box are device pointers; NULL gives zeros and that input is not read.
+ * S == 0 gives zeros.  Limits as above plus beta finite and >= 0.  The forward's workspace is
+ * stream-ordered scratch of frcnn_rpn_losses_multi_workspace_size bytes, 256-byte aligned. */
+size_t frcnn_rpn_losses_multi_workspace_size(int N, int batch_size_per_image);
+int frcnn_rpn_losses_multi_fwd_t(int dtype, int n_levels, const void* const* objectness, const void* const* deltas,
+                                 const int* H, const int* W, int N, int K, int batch_size_per_image,
+                                 const int32_t* samples, const int32_t* n_pos, const int32_t* n_neg,
+                                 const float* reg_targets, double beta, float* loss, int32_t* stats, void* workspace,
+                                 size_t ws_bytes, void* stream);
+int frcnn_rpn_losses_multi_bwd_t(int dtype, int n_levels, const void* const* objectness, const void* const* deltas,
+                                 const int* H, const int* W, int N, int K, int batch_size_per_image,
+                                 const int32_t* sampled, const int32_t* samples, const int32_t* n_pos,
+                                 const float* reg_targets, double beta, const int32_t* stats, const float* g_obj,
+                                 const float* g_box, void* const* dobjectness, void* const* ddeltas, void* stream);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

@@ -87,6 +87,13 @@ SIGNATURES = {
     "frcnn_propose_multi_t": (I32, [I32, I32, P, P, P, P, P, P, P, I32, I32, P, I32, I32, F64, F32, F32, P, P, P, P, P, P,
                                     P, SZ, P]),
     "frcnn_propose_multi_kernel": (I32, [I32, I32, I32, I32, P, P, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_rpn_targets_multi_workspace_size": (SZ, [I32, I32, I32, P, P, I32, I32]),
+    "frcnn_rpn_targets_multi": (I32, [I32, P, P, P, P, P, I32, I32, P, P, I32, P, I32, F64, F64, F64, I32, I32,
+                                      P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_rpn_targets_multi_kernel": (I32, [I32, I32, I32, P, P, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_rpn_losses_multi_workspace_size": (SZ, [I32, I32]),
+    "frcnn_rpn_losses_multi_fwd_t": (I32, [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, SZ, P]),
+    "frcnn_rpn_losses_multi_bwd_t": (I32, [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, P, P, P]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),

@@ -23,6 +23,10 @@
   (no reference counterpart; DESIGN.md §3 "FPN proposals"), with
   ``pyramid_anchor_bases`` / ``pyramid_anchors`` (torchvision's ``AnchorGenerator``)
   and ``logit_threshold`` (its score threshold as a test on the raw logit).
+* ``rpn_targets_multilevel(...)`` / ``rpn_losses_multilevel(...)`` -- the training half of that
+  RPN: torchvision's ``assign_targets_to_anchors``, ``Matcher``, ``BalancedPositiveNegativeSampler``,
+  ``BoxCoder.encode`` and ``compute_loss`` over the pyramid, with ``sampler_state`` (no reference
+  counterpart; DESIGN.md §3 "Pyramid RPN training").
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
   detections for the whole batch (no reference counterpart; DESIGN.md
   "Detections").
@@ -56,7 +60,8 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   types").  ``boxes`` / ``rois`` / ``roi_inds`` stay fp32, ``argmax`` int32.
   The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
-* The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``roi_transform``,
+* The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``rpn_targets_multilevel``,
+  ``rpn_losses_multilevel``, ``roi_transform``,
   ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
@@ -69,6 +74,7 @@ Errors follow torchvision's ``TORCH_CHECK`` -> ``RuntimeError`` convention.
 """
 from __future__ import annotations
 
+import collections
 from typing import List, Tuple, Union
 
 import torch
@@ -939,6 +945,325 @@ def propose_multilevel(objectness, deltas, anchor_bases, strides, image_sizes, *
                                          float(min_size), *[_lib.ptr(t) for t in outs], _lib.ptr(ws), ws.numel(),
                                          _lib.stream_ptr()), op)
     return outs
+
+
+# ------------------------------------------------------- pyramid RPN training
+RPN_TARGETS_MAX_G, RPN_TARGETS_MAX_BATCH = 256, 1024
+RPNTargets = collections.namedtuple("RPNTargets", "matches sampled samples n_pos n_neg reg_targets")
+_rpnt_cache = {}   # shape key -> (H, W, stride_h, stride_w host arrays, A, workspace bytes)
+_rpnl_ws = {}      # (N, B) -> workspace bytes of the losses' forward
+
+
+def sampler_state(seed: int, device=None) -> torch.Tensor:
+    """The sampler's state for ``rpn_targets_multilevel``: an int64 device tensor ``(seed, calls)``
+    with ``calls = 0``.  The op reads it on the device and adds 1 to ``calls``, so every call --
+    a replayed graph included -- draws a fresh sample with nothing passed from the host."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise RuntimeError(f"sampler_state: seed must fit 64 bits; got {seed}")
+    if seed >= 1 << 63:
+        seed -= 1 << 64
+    return torch.tensor([seed, 0], dtype=torch.int64).to(device if device is not None else _lib.device())
+
+
+def _rpnt_device(op, name, t):
+    """The device every tensor of one call shares: that of its first tensor, which must be the
+    current device (the kernels launch on its current stream)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        got = f"{t.dtype} {t.device.type} tensor" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{op}: {name} must be a device tensor; got a {got}")
+    if t.device.index != _lib._cur_device():
+        raise RuntimeError(f"{op}: {name} is on {t.device} but the current device is cuda:{_lib._cur_device()}; "
+                           "the kernels launch on the current device's stream")
+    return t.device
+
+
+def _rpnt_tensor(op, name, t, dtype, shape, dev=None):
+    if isinstance(t, torch.Tensor) and t.is_cuda and dev is not None and t.device != dev:
+        raise RuntimeError(f"{op}: {name} is on {t.device} but the call's tensors are on {dev}; every tensor of one "
+                           "call lives on one device")
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous()
+            or tuple(t.shape) != tuple(shape)):
+        got = (f"{'contiguous' if t.is_contiguous() else 'strided'} {t.dtype} {t.device.type} tensor of shape "
+               f"{list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__)
+        raise RuntimeError(f"{op}: {name} must be a contiguous {dtype} device tensor of shape {list(shape)}; "
+                           f"got a {got}")
+
+
+def _rpnt_levels(op, K, strides, grid_sizes):
+    """((H, W, stride_h, stride_w), ...) and A with the limits checked."""
+    if not isinstance(grid_sizes, (list, tuple)) or not 1 <= len(grid_sizes) <= FPN_MAX_LEVELS:
+        raise RuntimeError(f"{op}: grid_sizes must list 1 to {FPN_MAX_LEVELS} (H, W) pairs")
+    L = len(grid_sizes)
+    if not isinstance(strides, (list, tuple)) or len(strides) != L:
+        raise RuntimeError(f"{op}: strides must list one (stride_h, stride_w) per level ({L})")
+    if not 1 <= K <= FPN_MAX_K:
+        raise RuntimeError(f"{op}: anchor_bases: K must be in [1, {FPN_MAX_K}]; got {K}")
+    levels, A = [], 0
+    for l, (hw, s) in enumerate(zip(grid_sizes, strides)):
+        try:
+            H, W = int(hw[0]), int(hw[1])
+        except (TypeError, ValueError, IndexError):
+            raise RuntimeError(f"{op}: grid_sizes[{l}] must be (H, W) ints; got {hw!r}") from None
+        try:
+            sh, sw = int(s[0]), int(s[1])
+        except (TypeError, ValueError, IndexError):
+            raise RuntimeError(f"{op}: strides[{l}] must be (stride_h, stride_w) ints; got {s!r}") from None
+        if H < 1 or W < 1 or K * H * W >= 1 << 24:
+            raise RuntimeError(f"{op}: grid_sizes[{l}] = {(H, W)}: H, W >= 1 and K*H*W < 2^24 are required")
+        if sh < 1 or sw < 1 or (H - 1) * sh >= 1 << 24 or (W - 1) * sw >= 1 << 24:
+            raise RuntimeError(f"{op}: strides[{l}] = {(sh, sw)}: strides >= 1 and (H-1)*stride_h, (W-1)*stride_w "
+                               "below 2^24 are required")
+        levels.append((H, W, sh, sw))
+        A += K * H * W
+    if A >= 1 << 31:
+        raise RuntimeError(f"{op}: grid_sizes: {A} anchors in all; A must be below 2^31")
+    return tuple(levels), A
+
+
+def _rpnt_arrays(levels):
+    L = len(levels)
+    return tuple((_lib.I32 * L)(*[v[i] for v in levels]) for i in range(4))
+
+
+def rpn_targets_multilevel_kernel(K, grid_sizes, N=1, G=1, batch_size_per_image=256, _key_bits=32) -> str:
+    """frcnn_rpn_targets_multi_kernel: the kernels a call of this shape launches, with the
+    part of the launch plan that the shape fixes (workgroups per image, the last one's anchors,
+    the boundary-bucket keys the selection sorts in LDS, the key digits its radix passes refine
+    beyond that, the 4096-anchor steps of one of its sweeps).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    L = len(grid_sizes)
+    H = (_lib.I32 * L)(*[int(s[0]) for s in grid_sizes])
+    W = (_lib.I32 * L)(*[int(s[1]) for s in grid_sizes])
+    buf = _lib.ctypes.create_string_buffer(256)
+    _lib.check(lib.frcnn_rpn_targets_multi_kernel(L, int(N), int(K), H, W, int(G), int(batch_size_per_image),
+                                                  int(_key_bits), buf, 256), "rpn_targets_multi_kernel")
+    return buf.value.decode()
+
+
+def rpn_targets_multilevel(gt_boxes, gt_count, anchor_bases, strides, grid_sizes, rng, *,
+                           batch_size_per_image: int = 256, positive_fraction: float = 0.5,
+                           fg_iou_thresh: float = 0.7, bg_iou_thresh: float = 0.3,
+                           allow_low_quality_matches: bool = True, out=None, workspace=None, _key_bits: int = 32):
+    """The training targets of a pyramid RPN: torchvision's ``assign_targets_to_anchors``
+    (``box_iou``, ``Matcher(fg, bg, allow_low_quality_matches)``), ``BalancedPositiveNegativeSampler``
+    and ``BoxCoder.encode`` with weights (1, 1, 1, 1) for the whole batch and pyramid, five
+    launches, no host synchronisation (frcnn_rpn_targets_multi; DESIGN.md §3 "Pyramid RPN
+    training" is the contract).
+
+    ``gt_boxes``: fp32 device tensor [N, G, 4] of (x1, y1, x2, y2); ``gt_count``: int32 device
+    tensor [N], rows past it are padding (clamped to [0, G]); ``anchor_bases``, ``strides``,
+    ``grid_sizes``: as ``pyramid_anchors`` takes them, the bases on the device -- the anchors are
+    formed in registers, global index ``off_l + (y*W_l + x)*K + k``, the row order of
+    ``torch.cat(pyramid_anchors(...))``; ``rng``: ``sampler_state(seed)``, read on the device and
+    advanced by the call.
+
+    A gt row that is not finite or has no positive width and height is treated as absent.  The
+    sample is the ``num_pos`` positives and ``num_neg`` negatives with the smallest (Philox key,
+    anchor index): exact, reproducible from ``rng``, the same bits on every call.
+
+    Returns ``RPNTargets(matches int32 [N, A] (-1 below bg, -2 between, else the gt index),
+    sampled int32 [N, A] (1 / 0 / -1), samples int32 [N, B] (positives ascending, negatives
+    ascending, -1), n_pos, n_neg int32 [N], reg_targets fp32 [N, B, 4])``.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device or a strided view raises
+    RuntimeError naming the argument before any launch.  Every tensor of a call -- inputs, bases,
+    ``rng``, ``out``, ``workspace`` -- lives on one device, the current one (the kernels launch on
+    its current stream).  ``out``: the six outputs, caller-owned;
+    ``workspace``: a uint8 device tensor of at least the cached size.  ``_key_bits`` (a test knob)
+    keeps only that many top bits of every key: with 0 every key ties and the sample is the
+    first candidates by index."""
+    op = "rpn_targets_multilevel"
+    lib = _lib.load()
+    if not isinstance(gt_boxes, torch.Tensor) or gt_boxes.dim() != 3:
+        raise RuntimeError(f"{op}: gt_boxes must be an fp32 device tensor of shape [N, G, 4]")
+    N, G = int(gt_boxes.shape[0]), int(gt_boxes.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: gt_boxes: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= G <= RPN_TARGETS_MAX_G:
+        raise RuntimeError(f"{op}: gt_boxes: G must be in [1, {RPN_TARGETS_MAX_G}]; got {G}")
+    _rpnt_tensor(op, "gt_boxes", gt_boxes, torch.float32, (N, G, 4))
+    dev = _rpnt_device(op, "gt_boxes", gt_boxes)
+    _rpnt_tensor(op, "gt_count", gt_count, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "rng", rng, torch.int64, (2,), dev)
+    if not isinstance(anchor_bases, (list, tuple)) or not 1 <= len(anchor_bases) <= FPN_MAX_LEVELS:
+        raise RuntimeError(f"{op}: anchor_bases must be a list of 1 to {FPN_MAX_LEVELS} fp32 device tensors [K, 4]")
+    b0 = anchor_bases[0]
+    if not isinstance(b0, torch.Tensor) or b0.dim() != 2:
+        raise RuntimeError(f"{op}: anchor_bases[0] must be an fp32 device tensor of shape [K, 4]")
+    K = int(b0.shape[0])
+    B = int(batch_size_per_image)
+    if not 1 <= B <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: batch_size_per_image must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {B}")
+    frac, fg, bg = float(positive_fraction), float(fg_iou_thresh), float(bg_iou_thresh)
+    if not 0.0 <= frac <= 1.0:
+        raise RuntimeError(f"{op}: positive_fraction must be in [0, 1]; got {frac}")
+    if not bg <= fg:
+        raise RuntimeError(f"{op}: bg_iou_thresh = {bg} must not exceed fg_iou_thresh = {fg}")
+    kb = int(_key_bits)
+    if not 0 <= kb <= 32:
+        raise RuntimeError(f"{op}: _key_bits must be in [0, 32]; got {kb}")
+    try:
+        key0 = (K, tuple(tuple(int(v) for v in s) for s in strides), tuple(tuple(int(v) for v in s) for s in grid_sizes),
+                N, G, B)
+    except (TypeError, ValueError):
+        _rpnt_levels(op, K, strides, grid_sizes)   # raises, naming the argument
+        raise RuntimeError(f"{op}: strides and grid_sizes must list (stride_h, stride_w) / (H, W) ints") from None
+    cached = _rpnt_cache.get(key0)
+    if cached is None:
+        levels, A = _rpnt_levels(op, K, strides, grid_sizes)
+        arrays = _rpnt_arrays(levels)
+        need = int(lib.frcnn_rpn_targets_multi_workspace_size(len(levels), N, K, arrays[0], arrays[1], G, B))
+        if need == 0:
+            raise RuntimeError(f"{op}: {lib.frcnn_last_error().decode()}")
+        cached = _rpnt_cache[key0] = arrays + (A, need)
+    Hs, Ws, shs, sws, A, need = cached
+    L = len(Hs)
+    if len(anchor_bases) != L:
+        raise RuntimeError(f"{op}: anchor_bases must list one tensor per level ({L})")
+    for l in range(L):
+        _rpnt_tensor(op, f"anchor_bases[{l}]", anchor_bases[l], torch.float32, (K, 4), dev)
+    shapes = (((N, A), torch.int32, "matches"), ((N, A), torch.int32, "sampled"), ((N, B), torch.int32, "samples"),
+              ((N,), torch.int32, "n_pos"), ((N,), torch.int32, "n_neg"), ((N, B, 4), torch.float32, "reg_targets"))
+    if out is None:
+        outs = tuple(torch.empty(s, dtype=d, device=dev) for s, d, _ in shapes)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != 6:
+            raise RuntimeError(f"{op}: out must be the six outputs (matches, sampled, samples, n_pos, n_neg, "
+                               "reg_targets)")
+        outs = tuple(out)
+        for i, (s, d, nm) in enumerate(shapes):
+            _rpnt_tensor(op, f"out[{i}] ({nm})", outs[i], d, s, dev)
+    ws = workspace if workspace is not None else _lib.cached_workspace(op, need, dev)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous()
+            or ws.numel() < need or ws.device != dev):
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 tensor of at least {need} B on {dev}")
+    P = _lib.P
+    _lib.check(lib.frcnn_rpn_targets_multi(L, (P * L)(*[t.data_ptr() for t in anchor_bases]), Hs, Ws, shs, sws, N, K,
+                                           _lib.ptr(gt_boxes), _lib.ptr(gt_count), G, _lib.ptr(rng), B, frac, fg, bg,
+                                           int(bool(allow_low_quality_matches)), kb, *[_lib.ptr(t) for t in outs],
+                                           _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), op)
+    return RPNTargets(*outs)
+
+
+class _RPNLossesMultiFunction(torch.autograd.Function):
+    """frcnn_rpn_losses_multi_fwd_t / _bwd_t.  ``args`` = the L objectness maps, then the L
+    deltas maps; the backward hands the incoming gradients to the kernel as device pointers
+    (an unused loss: None -> NULL -> that gradient all zero)."""
+
+    @staticmethod
+    def forward(ctx, targets, beta, code, L, *maps):
+        lib = _lib.load()
+        obj, dl = maps[:L], maps[L:]
+        N, K = obj[0].shape[0], obj[0].shape[1]
+        B = targets.samples.shape[1]
+        dev = obj[0].device
+        Hs = (_lib.I32 * L)(*[t.shape[2] for t in obj])
+        Ws = (_lib.I32 * L)(*[t.shape[3] for t in obj])
+        need = _rpnl_ws.get((N, B))
+        if need is None:
+            need = _rpnl_ws[(N, B)] = int(lib.frcnn_rpn_losses_multi_workspace_size(N, B))
+        ws = _lib.cached_workspace("rpn_losses_multilevel", need, dev)
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        stats = torch.empty(2, dtype=torch.int32, device=dev)
+        P = _lib.P
+        po, pd = (P * L)(*[t.data_ptr() for t in obj]), (P * L)(*[t.data_ptr() for t in dl])
+        _lib.check(lib.frcnn_rpn_losses_multi_fwd_t(code, L, po, pd, Hs, Ws, N, K, B, _lib.ptr(targets.samples),
+                                                    _lib.ptr(targets.n_pos), _lib.ptr(targets.n_neg),
+                                                    _lib.ptr(targets.reg_targets), beta, _lib.ptr(loss),
+                                                    _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "rpn_losses_multilevel forward")
+        ctx.save_for_backward(*maps, targets.sampled, targets.samples, targets.n_pos, targets.reg_targets, stats)
+        ctx.meta = (beta, code, L, N, K, B, Hs, Ws)
+        ctx.set_materialize_grads(False)
+        return loss[0], loss[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_obj, g_box):
+        lib = _lib.load()
+        beta, code, L, N, K, B, Hs, Ws = ctx.meta
+        saved = ctx.saved_tensors
+        maps = saved[:2 * L]
+        sampled, samples, n_pos, reg_t, stats = saved[2 * L:]
+        for name, g in (("objectness_loss", g_obj), ("box_loss", g_box)):
+            if g is not None and (g.dtype != torch.float32 or not g.is_cuda or g.numel() != 1):
+                raise RuntimeError(f"rpn_losses_multilevel backward: the gradient of {name} must be one torch.float32 "
+                                   f"on the device; got {g.dtype} on {g.device.type} with {g.numel()} elements")
+        grads = [torch.empty_like(t) for t in maps]   # contiguous, the inputs' dtype: each element is stored once
+        P = _lib.P
+        _lib.check(lib.frcnn_rpn_losses_multi_bwd_t(code, L, (P * L)(*[t.data_ptr() for t in maps[:L]]),
+                                                    (P * L)(*[t.data_ptr() for t in maps[L:]]), Hs, Ws, N, K, B,
+                                                    _lib.ptr(sampled), _lib.ptr(samples), _lib.ptr(n_pos),
+                                                    _lib.ptr(reg_t), beta, _lib.ptr(stats), _lib.ptr(g_obj),
+                                                    _lib.ptr(g_box), (P * L)(*[t.data_ptr() for t in grads[:L]]),
+                                                    (P * L)(*[t.data_ptr() for t in grads[L:]]), _lib.stream_ptr()),
+                   "rpn_losses_multilevel backward")
+        return (None, None, None, None, *grads)
+
+
+def rpn_losses_multilevel(objectness, deltas, targets, *, beta: float = 1 / 9):
+    """torchvision's ``RegionProposalNetwork.compute_loss`` on ``rpn_targets_multilevel``'s
+    result, differentiable with respect to every tensor of ``objectness`` and ``deltas``
+    (frcnn_rpn_losses_multi_fwd_t / _bwd_t; DESIGN.md §3 "Pyramid RPN training").
+
+    ``objectness``: L tensors [N, K, H_l, W_l]; ``deltas``: L tensors [N, 4K, H_l, W_l] (channel
+    4k + c) -- the lists ``propose_multilevel`` reads, contiguous, all fp32, float16 or bfloat16,
+    read in place; ``targets``: the ``RPNTargets`` of the same pyramid.  Returns
+    ``(objectness_loss, box_loss)``, 0-dim fp32 device tensors: the mean over the S sampled
+    anchors of the binary cross-entropy with logits, and the smooth-L1 (``beta``) sum over the
+    sampled positives divided by S.  S == 0 gives NaN and zero gradients.
+
+    The forward reads the S samples only; the backward writes every level's gradient in full,
+    each element once, in the inputs' dtype, with no atomics: the same bits on every call.
+    Nothing is converted and nothing synchronises; a wrong dtype, shape, device or a strided view
+    raises RuntimeError naming the argument before any launch, and so does a tensor -- of the maps or
+    of ``targets`` -- that is not on ``objectness[0]``'s device, which must be the current one."""
+    op = "rpn_losses_multilevel"
+    _lib.load()
+    if not isinstance(objectness, (list, tuple)) or not 1 <= len(objectness) <= FPN_MAX_LEVELS:
+        raise RuntimeError(f"{op}: objectness must be a list of 1 to {FPN_MAX_LEVELS} tensors [N, K, H, W]")
+    L = len(objectness)
+    if not isinstance(deltas, (list, tuple)) or len(deltas) != L:
+        raise RuntimeError(f"{op}: deltas must list one tensor per level ({L})")
+    if not isinstance(targets, RPNTargets):
+        raise RuntimeError(f"{op}: targets must be the RPNTargets of rpn_targets_multilevel; got "
+                           f"{type(targets).__name__}")
+    code = _lib.prediction_dtype_code(op, [(f"objectness[{l}]", t) for l, t in enumerate(objectness)] +
+                                      [(f"deltas[{l}]", t) for l, t in enumerate(deltas)])
+    o0 = objectness[0]
+    if o0.dim() != 4:
+        raise RuntimeError(f"{op}: objectness[0] must be a device tensor of shape [N, K, H, W]")
+    N, K = int(o0.shape[0]), int(o0.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: objectness: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= K <= FPN_MAX_K:
+        raise RuntimeError(f"{op}: objectness: K must be in [1, {FPN_MAX_K}]; got {K}")
+    dev = _rpnt_device(op, "objectness[0]", o0)
+    A = 0
+    for l, o in enumerate(objectness):
+        if o.dim() != 4:
+            raise RuntimeError(f"{op}: objectness[{l}] must be a device tensor of shape [N, K, H, W]")
+        H, W = int(o.shape[2]), int(o.shape[3])
+        if H < 1 or W < 1 or K * H * W >= 1 << 24:
+            raise RuntimeError(f"{op}: objectness[{l}]: H, W >= 1 and K*H*W < 2^24 are required; got {list(o.shape)}")
+        _rpnt_tensor(op, f"objectness[{l}]", o, o0.dtype, (N, K, H, W), dev)
+        _rpnt_tensor(op, f"deltas[{l}]", deltas[l], o0.dtype, (N, 4 * K, H, W), dev)
+        A += K * H * W
+    if targets.samples.dim() != 2:
+        raise RuntimeError(f"{op}: targets.samples must be an int32 device tensor of shape [N, B]")
+    B = int(targets.samples.shape[1])
+    if not 1 <= B <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: targets.samples: B must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {B}")
+    _rpnt_tensor(op, "targets.sampled", targets.sampled, torch.int32, (N, A), dev)
+    _rpnt_tensor(op, "targets.samples", targets.samples, torch.int32, (N, B), dev)
+    _rpnt_tensor(op, "targets.n_pos", targets.n_pos, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "targets.n_neg", targets.n_neg, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "targets.reg_targets", targets.reg_targets, torch.float32, (N, B, 4), dev)
+    beta = float(beta)
+    if not 0.0 <= beta < float("inf"):
+        raise RuntimeError(f"{op}: beta={beta} must be finite and not negative")
+    return _RPNLossesMultiFunction.apply(targets, beta, code, L, *objectness, *deltas)
 
 
 # ----------------------------------------------------------------- detections

@@ -7,6 +7,11 @@ nets/rpn.py:131-136 becomes one launch sequence over the whole batch, with
 anchors generated inside the decode kernel.  The conv outputs' permutes and
 the fg softmax are one HIP launch (``ops.rpn_head_epilogue``); the 3x3/1x1
 convolutions stay plain PyTorch (not the target).
+
+``MultiLevelProposals`` and ``MultiLevelRPNTraining`` are the two halves of torchvision's
+``RegionProposalNetwork`` for an FPN head: ``filter_proposals`` and the training targets, sampler
+and losses, on ``ops.propose_multilevel`` and ``ops.rpn_targets_multilevel`` /
+``ops.rpn_losses_multilevel``.
 """
 from __future__ import annotations
 
@@ -156,3 +161,34 @@ class MultiLevelProposals(nn.Module):
         counts = count.tolist()  # the one host sync: the lists' lengths are data-dependent
         return ([boxes[i, :c] for i, c in enumerate(counts)],
                 [torch.sigmoid(logits[i, :c]) for i, c in enumerate(counts)])
+
+
+class MultiLevelRPNTraining(nn.Module):
+    """The training half of torchvision's ``RegionProposalNetwork`` for an FPN RPN head:
+    ``assign_targets_to_anchors`` (``Matcher(fg_iou_thresh, bg_iou_thresh,
+    allow_low_quality_matches=True)``), ``BalancedPositiveNegativeSampler(batch_size_per_image,
+    positive_fraction)``, ``BoxCoder.encode`` and ``compute_loss`` on ``ops.rpn_targets_multilevel``
+    and ``ops.rpn_losses_multilevel``.  The sampler's ``(seed, calls)`` state is a buffer of the
+    module, advanced on the device by every forward; nothing synchronises."""
+
+    def __init__(self, fg_iou_thresh=0.7, bg_iou_thresh=0.3, batch_size_per_image=256, positive_fraction=0.5, seed=0):
+        super().__init__()
+        self.fg_iou_thresh = fg_iou_thresh
+        self.bg_iou_thresh = bg_iou_thresh
+        self.batch_size_per_image = batch_size_per_image
+        self.positive_fraction = positive_fraction
+        self.register_buffer("rng", ops.sampler_state(seed, device="cpu"))
+
+    def forward(self, objectness, deltas, gt_boxes, gt_count, anchor_bases, strides):
+        """-> (objectness_loss, box_loss, RPNTargets).  ``objectness`` / ``deltas``: the head's
+        per-level NCHW outputs, as ``MultiLevelProposals`` takes them; ``gt_boxes`` fp32
+        [N, G, 4], ``gt_count`` int32 [N]."""
+        if self.rng.device != gt_boxes.device:
+            self.rng = self.rng.to(gt_boxes.device)
+        grid_sizes = [(int(o.shape[2]), int(o.shape[3])) for o in objectness]
+        targets = ops.rpn_targets_multilevel(gt_boxes, gt_count, anchor_bases, strides, grid_sizes, self.rng,
+                                             batch_size_per_image=self.batch_size_per_image,
+                                             positive_fraction=self.positive_fraction,
+                                             fg_iou_thresh=self.fg_iou_thresh, bg_iou_thresh=self.bg_iou_thresh)
+        obj_loss, box_loss = ops.rpn_losses_multilevel(objectness, deltas, targets)
+        return obj_loss, box_loss, targets
