@@ -500,6 +500,82 @@ int frcnn_rpn_losses_multi_bwd_t(int dtype, int n_levels, const void* const* obj
                                  const float* reg_targets, double beta, const int32_t* stats, const float* g_obj,
                                  const float* g_box, void* const* dobjectness, void* const* ddeltas, void* stream);
 
+/* Pyramid box-head training targets: torchvision's RoIHeads.select_training_samples
+ * (add_gt_proposals, box_iou + Matcher(fg, bg, allow_low_quality_matches=False),
+ * assign_targets_to_proposals, BalancedPositiveNegativeSampler, BoxCoder.encode with weights) for
+ * a whole batch (DESIGN.md §3 "Pyramid box-head training" is the contract).  Two launches
+ * on `stream`, no host synchronisation, no floating-point atomics; fp32 with every operation
+ * rounded separately; the same bits on every call.
+ *   proposals fp32 [N,R,4] (x1,y1,x2,y2), prop_count int32 [N] (clamped to [0,R]): what
+ *   frcnn_propose_multi_t wrote as boxes / count; gt_boxes fp32 [N,G,4], gt_labels int32 [N,G],
+ *   gt_count int32 [N] (clamped to [0,G]); rng int64 [2] = (seed, calls) on the device, read by
+ *   the first launch; the last one stores calls + 1 and nothing reads rng behind that store.
+ * Candidates of an image, M = R + G: index c < R is proposal c, present iff c < prop_count;
+ * index R + g is gt row g, present iff add_gt and the row is present (g < gt_count, finite,
+ * x2 > x1, y2 > y1: the rule of frcnn_rpn_targets_multi).  IoU as there (no intersection is 0, a
+ * NaN quotient is 0); the largest over the present gt rows, lowest index on a tie;
+ * matches[n,c] = -1 below (float)bg, -2 in [bg, fg), else the gt index; -3 for an absent
+ * candidate; an image without a present gt row has -1 for every present candidate.  label =
+ * gt_labels[match], 0 for -1, -1 for -2; positive iff label >= 1, negative iff label == 0.
+ * num_pos = min(P, (int)(B * positive_fraction)), num_neg = min(Ng, B - num_pos); chosen are
+ * the candidates of each class with the smallest (key, index), key = word 0 of Philox4x32-10
+ * with counter (index, n, calls lo, calls hi) and key (seed lo, seed hi), its low 32 - key_bits
+ * bits cleared (key_bits = 32 outside tests).
+ * Outputs, B slots per image, the chosen candidates in ascending index order (positives and
+ * negatives interleaved), then padding; every element is stored on every call:
+ *   rois fp32 [N*B,5] (n, x1, y1, x2, y2) with the candidate's bits, padding (-1,0,0,0,0): the
+ *   RoI rows of frcnn_roi_align_multi_fwd_t; labels int32 [N,B], padding -1; matched int32
+ *   [N,B]: the gt index of a positive, 0 of a negative, padding -1; reg_targets fp32 [N,B,4]:
+ *   for a positive w = x2 - x1, cx = x1 + 0.5*w of proposal and gt, ((float)wx * (gcx - cx)) / w
+ *   and (float)ww * log(gw / w) with a correctly rounded log, else 0; samples int32 [N,B]: the
+ *   candidate index, padding -1; n_pos, n_neg int32 [N]; matches int32 [N,M].
+ * Limits: N in [1,1024], R in [1,4096], G in [1,256], batch_size_per_image in [1,1024],
+ * positive_fraction in [0,1], bg <= fg, weights finite and positive, key_bits in [0,32].
+ * proposals, gt_boxes, reg_targets 16-byte aligned, rng 8-byte.  The workspace is stream-ordered
+ * scratch, 256-byte aligned; its contents on entry do not matter. */
+size_t frcnn_box_head_targets_workspace_size(int N, int R, int G, int batch_size_per_image);
+int frcnn_box_head_targets(const float* proposals, const int32_t* prop_count, int N, int R, const float* gt_boxes,
+                           const int32_t* gt_labels, const int32_t* gt_count, int G, int64_t* rng,
+                           int batch_size_per_image, double positive_fraction, double fg_iou_thresh,
+                           double bg_iou_thresh, double wx, double wy, double ww, double wh, int add_gt, int key_bits,
+                           float* rois, int32_t* labels, int32_t* matched, float* reg_targets, int32_t* samples,
+                           int32_t* n_pos, int32_t* n_neg, int32_t* matches, void* workspace, size_t ws_bytes,
+                           void* stream);
+/* Host only: the kernels a call of this shape launches with what the shape fixes of the plan:
+ * M, the match kernel's workgroups per image and the candidates of the last one, the candidates
+ * per thread of the sample kernel's slot scan, and the 12-bit digits its exact selection may
+ * walk (how many it does walk depends on the data: none for a class taken whole):
+ * "bht_match_kernel[M=1032,blocks=5,tail=8] bht_sample_kernel[per=2,digits=4x12]". */
+int frcnn_box_head_targets_kernel(int N, int R, int G, int batch_size_per_image, int key_bits, char* name, size_t len);
+
+/* Pyramid box-head losses: torchvision's fastrcnn_loss on the targets above, forward and
+ * backward.  class_logits `dtype` [N*B,C], box_regression `dtype` [N*B,4C] (column 4c + j),
+ * widened exactly at the load.  Slot j of image n is valid iff j < n_pos[n] + n_neg[n] (clamped
+ * to B) and its label is >= 0; a valid slot whose label is >= C is skipped and counted in
+ * stats[2], never used as an index.  S = the valid slots that are not skipped.
+ * Forward: per row, one wave: m = max x, e_c = exp(x_c - m) correctly rounded, their sum with
+ * each lane adding classes (lane, lane + 64) in that order and then a butterfly from 32 down to
+ * 1, the term log(sum) - (x_label - m) with a correctly rounded log; for a positive (label >= 1)
+ * the four columns 4*label + j: z = |x - target|, z < (float)beta ? 0.5*z*z/beta : z - 0.5*beta.
+ * The terms are added in fp64 in a fixed order; loss[0] = class sum / S, loss[1] = box sum / S,
+ * each rounded once (S == 0: NaN); stats = (S, positives, skipped, 0).
+ * Backward: every element of dclass_logits / dbox_regression stored exactly once in `dtype`:
+ * (e_c / sum - (c == label)) * (*g_cls / S) on a valid row, (z < beta ? (x - target)/beta :
+ * sign(x - target)) * (*g_box / S) on a positive's four label columns, +0 elsewhere; fp32,
+ * rounded once at the store.  g_cls / g_box are device pointers; NULL gives zeros and that
+ * input is not read.  S == 0 gives zeros.  No atomics.  Limits: N, B as above, C in [2,128],
+ * beta finite and >= 0.  The forward's workspace is stream-ordered scratch, 256-byte aligned. */
+size_t frcnn_box_head_losses_workspace_size(int N, int batch_size_per_image);
+int frcnn_box_head_losses_fwd_t(int dtype, const void* class_logits, const void* box_regression, int N,
+                                int batch_size_per_image, int C, const int32_t* labels, const float* reg_targets,
+                                const int32_t* n_pos, const int32_t* n_neg, double beta, float* loss, int32_t* stats,
+                                void* workspace, size_t ws_bytes, void* stream);
+int frcnn_box_head_losses_bwd_t(int dtype, const void* class_logits, const void* box_regression, int N,
+                                int batch_size_per_image, int C, const int32_t* labels, const float* reg_targets,
+                                const int32_t* n_pos, const int32_t* n_neg, double beta, const int32_t* stats,
+                                const float* g_cls, const float* g_box, void* dclass_logits, void* dbox_regression,
+                                void* stream);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

@@ -94,6 +94,13 @@ SIGNATURES = {
     "frcnn_rpn_losses_multi_workspace_size": (SZ, [I32, I32]),
     "frcnn_rpn_losses_multi_fwd_t": (I32, [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, SZ, P]),
     "frcnn_rpn_losses_multi_bwd_t": (I32, [I32, I32, P, P, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, P, P, P]),
+    "frcnn_box_head_targets_workspace_size": (SZ, [I32, I32, I32, I32]),
+    "frcnn_box_head_targets": (I32, [P, P, I32, I32, P, P, P, I32, P, I32, F64, F64, F64, F64, F64, F64, F64, I32, I32,
+                                     P, P, P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_box_head_targets_kernel": (I32, [I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_box_head_losses_workspace_size": (SZ, [I32, I32]),
+    "frcnn_box_head_losses_fwd_t": (I32, [I32, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, SZ, P]),
+    "frcnn_box_head_losses_bwd_t": (I32, [I32, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, P, P, P]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),

@@ -14,6 +14,11 @@ in their own type: ``cropped`` reaches the classifier in ``x``'s dtype and
 above, unchanged) pools with ``ops.roi_align`` instead: ``ops.roi_transform``,
 then RoIAlign forward and its deterministic HIP backward (DESIGN.md §3
 "RoIAlign"), in ``x``'s dtype as well.
+
+``BoxHeadTraining`` is the training half of a box head on the pyramid path (torchvision's
+``RoIHeads.select_training_samples`` and ``fastrcnn_loss``; DESIGN.md §3 "Pyramid box-head
+training").  It stands beside ``ResnetHead``; neither it nor the pyramid ops are wired into
+``FasterRCNN``.
 """
 from __future__ import annotations
 
@@ -71,3 +76,40 @@ class ResnetHead(nn.Module):
         reg = reg.view(N, -1, reg.shape[-1])
         cls = cls.view(N, -1, cls.shape[-1])
         return cls.permute(0, 2, 1), reg
+
+
+class BoxHeadTraining(nn.Module):
+    """The training half of torchvision's ``RoIHeads`` for a box head on pooled pyramid features:
+    ``select_training_samples`` (``add_gt_proposals``, ``Matcher(fg_iou_thresh, bg_iou_thresh,
+    allow_low_quality_matches=False)``, ``BalancedPositiveNegativeSampler(batch_size_per_image,
+    positive_fraction)``, ``BoxCoder(reg_weights).encode``) on ``ops.box_head_targets`` and
+    ``fastrcnn_loss`` on ``ops.box_head_losses``.  The sampler's ``(seed, calls)`` state is a
+    buffer of the module, advanced on the device by every ``targets`` call; nothing synchronises.
+
+    ``targets(...).rois`` feeds ``ops.multiscale_roi_align`` as it is; the head's two predictions
+    for those rows go to ``losses``."""
+
+    def __init__(self, fg_iou_thresh=0.5, bg_iou_thresh=0.5, batch_size_per_image=512, positive_fraction=0.25,
+                 reg_weights=(10, 10, 5, 5), seed=0):
+        super().__init__()
+        self.fg_iou_thresh = fg_iou_thresh
+        self.bg_iou_thresh = bg_iou_thresh
+        self.batch_size_per_image = batch_size_per_image
+        self.positive_fraction = positive_fraction
+        self.reg_weights = tuple(float(w) for w in reg_weights)
+        self.register_buffer("rng", ops.sampler_state(seed, device="cpu"))
+
+    def targets(self, proposals, prop_count, gt_boxes, gt_labels, gt_count):
+        """-> ``ops.BoxHeadTargets``.  ``proposals`` fp32 [N, R, 4] and ``prop_count`` int32 [N] as
+        ``ops.propose_multilevel`` returns them; ``gt_boxes`` fp32 [N, G, 4], ``gt_labels`` int32
+        [N, G], ``gt_count`` int32 [N]."""
+        if self.rng.device != proposals.device:
+            self.rng = self.rng.to(proposals.device)
+        return ops.box_head_targets(proposals, prop_count, gt_boxes, gt_labels, gt_count, self.rng,
+                                    batch_size_per_image=self.batch_size_per_image,
+                                    positive_fraction=self.positive_fraction, fg_iou_thresh=self.fg_iou_thresh,
+                                    bg_iou_thresh=self.bg_iou_thresh, reg_weights=self.reg_weights)
+
+    def losses(self, class_logits, box_regression, targets, beta=1 / 9):
+        """-> (classification_loss, box_loss) of the head's predictions for ``targets.rois``."""
+        return ops.box_head_losses(class_logits, box_regression, targets, beta=beta)

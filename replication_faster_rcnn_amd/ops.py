@@ -27,6 +27,10 @@
   RPN: torchvision's ``assign_targets_to_anchors``, ``Matcher``, ``BalancedPositiveNegativeSampler``,
   ``BoxCoder.encode`` and ``compute_loss`` over the pyramid, with ``sampler_state`` (no reference
   counterpart; DESIGN.md §3 "Pyramid RPN training").
+* ``box_head_targets(...)`` / ``box_head_losses(...)`` -- the training half of the box head behind
+  it: torchvision's ``select_training_samples`` (``add_gt_proposals``, ``Matcher``, the sampler,
+  ``BoxCoder.encode``) and ``fastrcnn_loss`` on ``propose_multilevel``'s proposals (no reference
+  counterpart; DESIGN.md §3 "Pyramid box-head training").
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
   detections for the whole batch (no reference counterpart; DESIGN.md
   "Detections").
@@ -61,7 +65,7 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
 * The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``rpn_targets_multilevel``,
-  ``rpn_losses_multilevel``, ``roi_transform``,
+  ``rpn_losses_multilevel``, ``box_head_targets``, ``box_head_losses``, ``roi_transform``,
   ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
@@ -1264,6 +1268,228 @@ def rpn_losses_multilevel(objectness, deltas, targets, *, beta: float = 1 / 9):
     if not 0.0 <= beta < float("inf"):
         raise RuntimeError(f"{op}: beta={beta} must be finite and not negative")
     return _RPNLossesMultiFunction.apply(targets, beta, code, L, *objectness, *deltas)
+
+
+# ------------------------------------------------- pyramid box-head training
+BOX_HEAD_MAX_R, BOX_HEAD_MAX_C = 4096, 128
+BoxHeadTargets = collections.namedtuple("BoxHeadTargets", "rois labels matched reg_targets samples n_pos n_neg matches")
+_bht_ws = {}   # (N, R, G, B) -> workspace bytes of the targets
+_bhl_ws = {}   # (N, B) -> workspace bytes of the losses' forward
+
+
+def box_head_targets_kernel(R, G, N=1, batch_size_per_image=512, _key_bits=32) -> str:
+    """frcnn_box_head_targets_kernel: the kernels a call of this shape launches, with the part
+    of the launch plan that the shape fixes (M = R + G, the match kernel's workgroups per image and
+    the candidates of the last one, the candidates per thread of the sample kernel's slot scan,
+    the digits its selection may walk).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    buf = _lib.ctypes.create_string_buffer(256)
+    _lib.check(lib.frcnn_box_head_targets_kernel(int(N), int(R), int(G), int(batch_size_per_image), int(_key_bits), buf,
+                                                 256), "box_head_targets_kernel")
+    return buf.value.decode()
+
+
+def box_head_targets(proposals, prop_count, gt_boxes, gt_labels, gt_count, rng, *, batch_size_per_image: int = 512,
+                     positive_fraction: float = 0.25, fg_iou_thresh: float = 0.5, bg_iou_thresh: float = 0.5,
+                     reg_weights=(10.0, 10.0, 5.0, 5.0), add_gt: bool = True, out=None, workspace=None,
+                     _key_bits: int = 32):
+    """The training samples of a box head: torchvision's ``RoIHeads.select_training_samples``
+    (``add_gt_proposals``, ``box_iou``, ``Matcher(fg, bg, allow_low_quality_matches=False)``,
+    ``assign_targets_to_proposals``, ``BalancedPositiveNegativeSampler``, ``BoxCoder.encode`` with
+    ``reg_weights``) for the whole batch, two launches, no host synchronisation
+    (frcnn_box_head_targets; DESIGN.md §3 "Pyramid box-head training" is the contract).
+
+    ``proposals``: fp32 device tensor [N, R, 4] of (x1, y1, x2, y2) and ``prop_count``: int32
+    [N] -- ``propose_multilevel``'s ``boxes`` and ``count``; ``gt_boxes`` fp32 [N, G, 4],
+    ``gt_labels`` int32 [N, G], ``gt_count`` int32 [N] (counts are clamped); ``rng``:
+    ``sampler_state(seed)``, read on the device and advanced by the call.
+
+    An image's candidates are its proposals below ``prop_count`` (index c) and, with ``add_gt``,
+    its present gt rows (index R + g; a row that is not finite or has no positive width and
+    height is absent).  The sample is the ``num_pos`` positives (label >= 1) and ``num_neg``
+    negatives (label 0) with the smallest (Philox key, index): exact, reproducible from ``rng``.
+
+    Returns ``BoxHeadTargets(rois fp32 [N*B, 5] (n, x1, y1, x2, y2), labels int32 [N, B],
+    matched int32 [N, B] (the gt index; 0 for a negative), reg_targets fp32 [N, B, 4] (0 for a
+    negative), samples int32 [N, B] (candidate indices), n_pos, n_neg int32 [N], matches int32
+    [N, R + G] (-1 below bg, -2 between, else the gt index, -3 absent))``.  The sampled
+    candidates fill an image's slots in ascending index order; the padding behind them is
+    ``rois`` (-1, 0, 0, 0, 0) -- a row ``multiscale_roi_align`` pools to zeros -- labels, matched
+    and samples -1, reg_targets 0.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device or a strided view raises
+    RuntimeError naming the argument before any launch.  Every tensor of a call lives on the
+    current device.  ``out``: the eight outputs, caller-owned; ``workspace``: a uint8 device
+    tensor of at least the cached size.  ``_key_bits`` (a test knob) keeps only that many top
+    bits of every key."""
+    op = "box_head_targets"
+    lib = _lib.load()
+    if not isinstance(proposals, torch.Tensor) or proposals.dim() != 3:
+        raise RuntimeError(f"{op}: proposals must be an fp32 device tensor of shape [N, R, 4]")
+    N, R = int(proposals.shape[0]), int(proposals.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: proposals: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= R <= BOX_HEAD_MAX_R:
+        raise RuntimeError(f"{op}: proposals: R must be in [1, {BOX_HEAD_MAX_R}]; got {R}")
+    _rpnt_tensor(op, "proposals", proposals, torch.float32, (N, R, 4))
+    dev = _rpnt_device(op, "proposals", proposals)
+    _rpnt_tensor(op, "prop_count", prop_count, torch.int32, (N,), dev)
+    if not isinstance(gt_boxes, torch.Tensor) or gt_boxes.dim() != 3:
+        raise RuntimeError(f"{op}: gt_boxes must be an fp32 device tensor of shape [N, G, 4]")
+    G = int(gt_boxes.shape[1])
+    if not 1 <= G <= RPN_TARGETS_MAX_G:
+        raise RuntimeError(f"{op}: gt_boxes: G must be in [1, {RPN_TARGETS_MAX_G}]; got {G}")
+    _rpnt_tensor(op, "gt_boxes", gt_boxes, torch.float32, (N, G, 4), dev)
+    _rpnt_tensor(op, "gt_labels", gt_labels, torch.int32, (N, G), dev)
+    _rpnt_tensor(op, "gt_count", gt_count, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "rng", rng, torch.int64, (2,), dev)
+    B = int(batch_size_per_image)
+    if not 1 <= B <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: batch_size_per_image must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {B}")
+    frac, fg, bg = float(positive_fraction), float(fg_iou_thresh), float(bg_iou_thresh)
+    if not 0.0 <= frac <= 1.0:
+        raise RuntimeError(f"{op}: positive_fraction must be in [0, 1]; got {frac}")
+    if not bg <= fg:
+        raise RuntimeError(f"{op}: bg_iou_thresh = {bg} must not exceed fg_iou_thresh = {fg}")
+    try:
+        wts = tuple(float(w) for w in reg_weights)
+    except (TypeError, ValueError):
+        wts = ()
+    if len(wts) != 4 or not all(0.0 < w < float("inf") for w in wts):
+        raise RuntimeError(f"{op}: reg_weights must be four finite positive numbers; got {reg_weights!r}")
+    kb = int(_key_bits)
+    if not 0 <= kb <= 32:
+        raise RuntimeError(f"{op}: _key_bits must be in [0, 32]; got {kb}")
+    need = _bht_ws.get((N, R, G, B))
+    if need is None:
+        need = int(lib.frcnn_box_head_targets_workspace_size(N, R, G, B))
+        if need == 0:
+            raise RuntimeError(f"{op}: {lib.frcnn_last_error().decode()}")
+        _bht_ws[(N, R, G, B)] = need
+    i32, f32 = torch.int32, torch.float32
+    shapes = (((N * B, 5), f32, "rois"), ((N, B), i32, "labels"), ((N, B), i32, "matched"),
+              ((N, B, 4), f32, "reg_targets"), ((N, B), i32, "samples"), ((N,), i32, "n_pos"), ((N,), i32, "n_neg"),
+              ((N, R + G), i32, "matches"))
+    if out is None:
+        outs = tuple(torch.empty(s, dtype=d, device=dev) for s, d, _ in shapes)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != 8:
+            raise RuntimeError(f"{op}: out must be the eight outputs (rois, labels, matched, reg_targets, samples, "
+                               "n_pos, n_neg, matches)")
+        outs = tuple(out)
+        for i, (s, d, nm) in enumerate(shapes):
+            _rpnt_tensor(op, f"out[{i}] ({nm})", outs[i], d, s, dev)
+    ws = workspace if workspace is not None else _lib.cached_workspace(op, need, dev)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous()
+            or ws.numel() < need or ws.device != dev):
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 tensor of at least {need} B on {dev}")
+    _lib.check(lib.frcnn_box_head_targets(_lib.ptr(proposals), _lib.ptr(prop_count), N, R, _lib.ptr(gt_boxes),
+                                          _lib.ptr(gt_labels), _lib.ptr(gt_count), G, _lib.ptr(rng), B, frac, fg, bg,
+                                          *wts, int(bool(add_gt)), kb, *[_lib.ptr(t) for t in outs], _lib.ptr(ws),
+                                          ws.numel(), _lib.stream_ptr()), op)
+    return BoxHeadTargets(*outs)
+
+
+class _BoxHeadLossesFunction(torch.autograd.Function):
+    """frcnn_box_head_losses_fwd_t / _bwd_t; the backward hands the incoming gradients to the
+    kernel as device pointers (an unused loss: None -> NULL -> that gradient all zero)."""
+
+    @staticmethod
+    def forward(ctx, targets, beta, code, cls, reg):
+        lib = _lib.load()
+        N, B = targets.labels.shape
+        C = cls.shape[1]
+        dev = cls.device
+        need = _bhl_ws.get((N, B))
+        if need is None:
+            need = _bhl_ws[(N, B)] = int(lib.frcnn_box_head_losses_workspace_size(N, B))
+        ws = _lib.cached_workspace("box_head_losses", need, dev)
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.frcnn_box_head_losses_fwd_t(code, _lib.ptr(cls), _lib.ptr(reg), N, B, C, _lib.ptr(targets.labels),
+                                                   _lib.ptr(targets.reg_targets), _lib.ptr(targets.n_pos),
+                                                   _lib.ptr(targets.n_neg), beta, _lib.ptr(loss), _lib.ptr(stats),
+                                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "box_head_losses forward")
+        ctx.save_for_backward(cls, reg, targets.labels, targets.reg_targets, targets.n_pos, targets.n_neg, stats)
+        ctx.meta = (beta, code, N, B, C)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(stats)
+        return loss[0], loss[1], stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls, g_box, _g_stats):
+        lib = _lib.load()
+        beta, code, N, B, C = ctx.meta
+        cls, reg, labels, reg_t, n_pos, n_neg, stats = ctx.saved_tensors
+        for name, g in (("classification_loss", g_cls), ("box_loss", g_box)):
+            if g is not None and (g.dtype != torch.float32 or not g.is_cuda or g.numel() != 1):
+                raise RuntimeError(f"box_head_losses backward: the gradient of {name} must be one torch.float32 on "
+                                   f"the device; got {g.dtype} on {g.device.type} with {g.numel()} elements")
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)   # each element is stored once
+        _lib.check(lib.frcnn_box_head_losses_bwd_t(code, _lib.ptr(cls), _lib.ptr(reg), N, B, C, _lib.ptr(labels),
+                                                   _lib.ptr(reg_t), _lib.ptr(n_pos), _lib.ptr(n_neg), beta,
+                                                   _lib.ptr(stats), _lib.ptr(g_cls), _lib.ptr(g_box), _lib.ptr(dcls),
+                                                   _lib.ptr(dreg), _lib.stream_ptr()), "box_head_losses backward")
+        return None, None, None, dcls, dreg
+
+
+def _box_head_losses(class_logits, box_regression, targets, beta):
+    op = "box_head_losses"
+    _lib.load()
+    if not isinstance(targets, BoxHeadTargets):
+        raise RuntimeError(f"{op}: targets must be the BoxHeadTargets of box_head_targets; got {type(targets).__name__}")
+    code = _lib.prediction_dtype_code(op, (("class_logits", class_logits), ("box_regression", box_regression)))
+    if class_logits.dim() != 2:
+        raise RuntimeError(f"{op}: class_logits must be a device tensor of shape [N*B, C]")
+    rows, C = int(class_logits.shape[0]), int(class_logits.shape[1])
+    if not 2 <= C <= BOX_HEAD_MAX_C:
+        raise RuntimeError(f"{op}: class_logits: C must be in [2, {BOX_HEAD_MAX_C}]; got {C}")
+    dev = _rpnt_device(op, "class_logits", class_logits)
+    if not isinstance(targets.labels, torch.Tensor) or targets.labels.dim() != 2:
+        raise RuntimeError(f"{op}: targets.labels must be an int32 device tensor of shape [N, B]")
+    N, B = int(targets.labels.shape[0]), int(targets.labels.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: targets.labels: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= B <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: targets.labels: B must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {B}")
+    _rpnt_tensor(op, "class_logits", class_logits, class_logits.dtype, (N * B, C), dev)
+    _rpnt_tensor(op, "box_regression", box_regression, class_logits.dtype, (N * B, 4 * C), dev)
+    _rpnt_tensor(op, "targets.labels", targets.labels, torch.int32, (N, B), dev)
+    _rpnt_tensor(op, "targets.reg_targets", targets.reg_targets, torch.float32, (N, B, 4), dev)
+    _rpnt_tensor(op, "targets.n_pos", targets.n_pos, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "targets.n_neg", targets.n_neg, torch.int32, (N,), dev)
+    beta = float(beta)
+    if not 0.0 <= beta < float("inf"):
+        raise RuntimeError(f"{op}: beta={beta} must be finite and not negative")
+    return _BoxHeadLossesFunction.apply(targets, beta, code, class_logits, box_regression)
+
+
+def box_head_losses(class_logits, box_regression, targets, *, beta: float = 1 / 9):
+    """torchvision's ``fastrcnn_loss`` on ``box_head_targets``' result, differentiable with
+    respect to both predictions (frcnn_box_head_losses_fwd_t / _bwd_t; DESIGN.md §3 "Pyramid
+    box-head training").
+
+    ``class_logits``: [N*B, C]; ``box_regression``: [N*B, 4C] (column 4c + j); both fp32, both
+    float16 or both bfloat16, contiguous, row ``n*B + slot`` as ``targets.rois`` orders them.
+    Returns ``(classification_loss, box_loss)``, 0-dim fp32 device tensors: the mean over the S
+    sampled slots of the cross-entropy, and the smooth-L1 (``beta``) sum over the positives'
+    four label columns divided by S.  Padding slots contribute nothing; a sampled slot whose
+    label is >= C is skipped and counted (``box_head_losses_with_stats``), never used as an index.
+    S == 0 gives NaN and zero gradients.
+
+    The backward stores every element of both gradients once, in the inputs' dtype, with no
+    atomics: the same bits on every call.  Nothing is converted and nothing synchronises; a wrong
+    dtype, shape, device or a strided view raises RuntimeError naming the argument before any
+    launch."""
+    return _box_head_losses(class_logits, box_regression, targets, beta)[:2]
+
+
+def box_head_losses_with_stats(class_logits, box_regression, targets, *, beta: float = 1 / 9):
+    """``box_head_losses`` plus ``stats``: int32 device tensor (S, sampled positives, slots
+    skipped for a label >= C, 0)."""
+    return _box_head_losses(class_logits, box_regression, targets, beta)
 
 
 # ----------------------------------------------------------------- detections
