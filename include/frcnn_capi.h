@@ -576,6 +576,48 @@ int frcnn_box_head_losses_bwd_t(int dtype, const void* class_logits, const void*
                                 const float* g_cls, const float* g_box, void* dclass_logits, void* dbox_regression,
                                 void* stream);
 
+/* Pyramid box-head inference: torchvision's RoIHeads.postprocess_detections (F.softmax,
+ * BoxCoder(weights).decode, box_ops.clip_boxes_to_image, the score_thresh test,
+ * box_ops.remove_small_boxes, box_ops.batched_nms in its _batched_nms_vanilla form, the first
+ * detections_per_img by score) and GeneralizedRCNNTransform.postprocess's resize_boxes, for a
+ * whole batch (DESIGN.md §3 "Pyramid box-head inference" is the contract).  Three launches on
+ * `stream`, no host synchronisation, no floating-point atomics; fp32 with every operation
+ * rounded separately; the same bits on every call.
+ *   class_logits `dtype` [N*R,C], box_regression `dtype` [N*R,4C] (column 4c + j), widened
+ *   exactly at the load; row n*R + r is proposal r of image n.  proposals fp32 [N,R,4]
+ *   (x1,y1,x2,y2), prop_count int32 [N] (clamped to [0,R]; rows past it are never read): what
+ *   frcnn_propose_multi_t wrote as boxes / count.  image_sizes fp32 [N,2] of (h,w);
+ *   original_sizes fp32 [N,2] of (h,w) or NULL.
+ * Row r < prop_count: m = max x, e_c = exp(x_c - m) correctly rounded, s = their sum in
+ * ascending class order, p_c = e_c * (1 / s) (frcnn_detect's rule).  (r, c), c >= 1, is a
+ * candidate iff p_c > score_thresh (a NaN never is).  Its box: w = x2 - x1, cx = x1 + 0.5*w,
+ * dx = reg[4c] / wx with a correctly rounded division, dw = min(reg[4c+2] / ww,
+ * (float)log(1000/16)) as torch.clamp(max=) (a NaN stays), pcx = dx*w + cx, pw = exp(dw)*w,
+ * x1' = pcx - 0.5*pw, x2' = pcx + 0.5*pw, the same in y; x clamped to [0, w_n], y to [0, h_n]
+ * as torch.clamp; kept iff x2' - x1' >= min_size and y2' - y1' >= min_size (a NaN fails).
+ * Greedy NMS per (image, class) in the order (p descending, r ascending), the test of
+ * frcnn_nms; classes never meet.  An image's kept boxes in the order (p descending, flat index
+ * r*(C-1) + (c-1) ascending): total[n] of them, the first count[n] = min(total[n],
+ * detections_per_img) written.  With original_sizes, x is multiplied by orig_w / w_n and y by
+ * orig_h / h_n (correctly rounded quotients) last of all.
+ * Outputs, every element stored exactly once per call: boxes fp32 [N,D,4] (padding 0), labels
+ * int32 [N,D] (-1), scores fp32 [N,D] (0), roi int32 [N,D] (the row r; -1), count, total int32 [N].
+ * Limits: N in [1,1024], R in [1,4096], C in [2,128], detections_per_img in [1,1024], weights
+ * finite and positive; boxes 16-byte aligned.  The workspace is stream-ordered scratch,
+ * 256-byte aligned, 4*N*R*C + 2*N*R*(C-1) + 4*N*(C-1) bytes with each of the three parts
+ * rounded up to 256; its contents on entry do not matter. */
+size_t frcnn_box_detections_workspace_size(int N, int R, int C);
+int frcnn_box_detections_t(int dtype, int N, int R, int C, const void* class_logits, const void* box_regression,
+                           const float* proposals, const int32_t* prop_count, const float* image_sizes,
+                           const float* original_sizes, float score_thresh, double nms_thresh, int detections_per_img,
+                           float min_size, float wx, float wy, float ww, float wh, float* boxes, int32_t* labels,
+                           float* scores, int32_t* roi, int32_t* count, int32_t* total, void* workspace,
+                           size_t ws_bytes, void* stream);
+/* Host only: the kernels a call of this shape launches, with the branch of the launch plan
+ * ("rows": R <= 1024, one thread per row; "strided": 1,024 threads, four rows each):
+ * "bd_score_kernel<ElemF32> bd_class_nms_kernel<ElemF32,1>[rows] bd_merge_kernel<ElemF32>". */
+int frcnn_box_detections_kernel(int dtype, int R, int C, int detections_per_img, char* name, size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

@@ -101,6 +101,10 @@ SIGNATURES = {
     "frcnn_box_head_losses_workspace_size": (SZ, [I32, I32]),
     "frcnn_box_head_losses_fwd_t": (I32, [I32, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, SZ, P]),
     "frcnn_box_head_losses_bwd_t": (I32, [I32, P, P, I32, I32, I32, P, P, P, P, F64, P, P, P, P, P, P]),
+    "frcnn_box_detections_workspace_size": (SZ, [I32, I32, I32]),
+    "frcnn_box_detections_t": (I32, [I32, I32, I32, I32, P, P, P, P, P, P, F32, F64, I32, F32, F32, F32, F32, F32,
+                                     P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_box_detections_kernel": (I32, [I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),

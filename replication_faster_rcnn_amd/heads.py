@@ -17,8 +17,10 @@ then RoIAlign forward and its deterministic HIP backward (DESIGN.md §3
 
 ``BoxHeadTraining`` is the training half of a box head on the pyramid path (torchvision's
 ``RoIHeads.select_training_samples`` and ``fastrcnn_loss``; DESIGN.md §3 "Pyramid box-head
-training").  It stands beside ``ResnetHead``; neither it nor the pyramid ops are wired into
-``FasterRCNN``.
+training").  ``BoxHeadDetections`` is the inference half: torchvision's
+``RoIHeads.postprocess_detections`` and the transform's ``resize_boxes`` on
+``ops.box_head_detections`` (DESIGN.md §3 "Pyramid box-head inference").  Both stand beside
+``ResnetHead``; neither they nor the pyramid ops are wired into ``FasterRCNN``.
 """
 from __future__ import annotations
 
@@ -113,3 +115,32 @@ class BoxHeadTraining(nn.Module):
     def losses(self, class_logits, box_regression, targets, beta=1 / 9):
         """-> (classification_loss, box_loss) of the head's predictions for ``targets.rois``."""
         return ops.box_head_losses(class_logits, box_regression, targets, beta=beta)
+
+
+class BoxHeadDetections(nn.Module):
+    """The inference half of torchvision's ``RoIHeads`` for a box head on pooled pyramid features:
+    ``postprocess_detections`` (softmax, ``BoxCoder(reg_weights).decode``, clip, ``score_thresh``,
+    ``remove_small_boxes(min_size)``, class-wise NMS at ``nms_thresh``, the best
+    ``detections_per_img``) on ``ops.box_head_detections``; nothing synchronises.
+
+    The result feeds ``evaluate.VOCEvaluator.update`` / ``COCOEvaluator.update`` as it is (boxes are
+    (x1, y1, x2, y2): give the ground truth in the same axis order)."""
+
+    def __init__(self, score_thresh=0.05, nms_thresh=0.5, detections_per_img=100, min_size=1e-2,
+                 reg_weights=(10, 10, 5, 5)):
+        super().__init__()
+        self.score_thresh = score_thresh
+        self.nms_thresh = nms_thresh
+        self.detections_per_img = detections_per_img
+        self.min_size = min_size
+        self.reg_weights = tuple(float(w) for w in reg_weights)
+
+    def forward(self, class_logits, box_regression, proposals, prop_count, image_sizes, original_sizes=None):
+        """-> ``ops.BoxDetections``.  ``class_logits`` [N*R, C] and ``box_regression`` [N*R, 4C]: the
+        head's outputs for ``ops.propose_multilevel``'s ``rois``; ``proposals`` / ``prop_count``: its
+        ``boxes`` / ``count``; ``image_sizes`` as it takes them; ``original_sizes``: fp32 device
+        tensor [N, 2] of (h, w) to map the boxes back to, or None."""
+        return ops.box_head_detections(class_logits, box_regression, proposals, prop_count, image_sizes,
+                                       score_thresh=self.score_thresh, nms_thresh=self.nms_thresh,
+                                       detections_per_img=self.detections_per_img, min_size=self.min_size,
+                                       reg_weights=self.reg_weights, original_sizes=original_sizes)

@@ -31,6 +31,10 @@
   it: torchvision's ``select_training_samples`` (``add_gt_proposals``, ``Matcher``, the sampler,
   ``BoxCoder.encode``) and ``fastrcnn_loss`` on ``propose_multilevel``'s proposals (no reference
   counterpart; DESIGN.md §3 "Pyramid box-head training").
+* ``box_head_detections(...)`` -- the inference half of that head: torchvision's
+  ``RoIHeads.postprocess_detections`` and the transform's ``resize_boxes`` on ``propose_multilevel``'s
+  proposals and the head's outputs (no reference counterpart; DESIGN.md §3 "Pyramid box-head
+  inference").
 * ``detect(...)`` -- head outputs -> per-class decoded, thresholded and NMS-ed
   detections for the whole batch (no reference counterpart; DESIGN.md
   "Detections").
@@ -65,14 +69,15 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   The same holds for float16 / bfloat16 conv outputs of ``rpn_head_epilogue``
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
 * The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``rpn_targets_multilevel``,
-  ``rpn_losses_multilevel``, ``box_head_targets``, ``box_head_losses``, ``roi_transform``,
+  ``rpn_losses_multilevel``, ``box_head_targets``, ``box_head_losses``, ``box_head_detections``, ``roi_transform``,
   ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
   The predictions ``cls`` / ``reg`` of ``detect``, ``rpn_losses`` and
   ``head_losses`` may be float16 or bfloat16 instead of fp32, both in the same
-  dtype (DESIGN.md §3 "Predictions in 16-bit types").
+  dtype (DESIGN.md §3 "Predictions in 16-bit types"); so may ``class_logits`` /
+  ``box_regression`` of ``box_head_losses`` and ``box_head_detections``.
 
 Errors follow torchvision's ``TORCH_CHECK`` -> ``RuntimeError`` convention.
 """
@@ -1490,6 +1495,131 @@ def box_head_losses_with_stats(class_logits, box_regression, targets, *, beta: f
     """``box_head_losses`` plus ``stats``: int32 device tensor (S, sampled positives, slots
     skipped for a label >= C, 0)."""
     return _box_head_losses(class_logits, box_regression, targets, beta)
+
+
+# ------------------------------------------------- pyramid box-head inference
+BOX_DET_MAX_D = 1024
+BoxDetections = collections.namedtuple("BoxDetections", "boxes labels scores roi count total")
+_bd_ws = {}   # (N, R, C) -> workspace bytes
+
+
+def _bd_shape(op, R, C, D):
+    R, C, D = int(R), int(C), int(D)
+    if not 1 <= R <= BOX_HEAD_MAX_R:
+        raise RuntimeError(f"{op}: proposals: R must be in [1, {BOX_HEAD_MAX_R}]; got {R}")
+    if not 2 <= C <= BOX_HEAD_MAX_C:
+        raise RuntimeError(f"{op}: class_logits: C must be in [2, {BOX_HEAD_MAX_C}]; got {C}")
+    if not 1 <= D <= BOX_DET_MAX_D:
+        raise RuntimeError(f"{op}: detections_per_img must be in [1, {BOX_DET_MAX_D}]; got {D}")
+    return R, C, D
+
+
+def box_head_detections_kernel(R, C, detections_per_img=100, dtype=torch.float32) -> str:
+    """frcnn_box_detections_kernel: the kernels a ``box_head_detections`` call of this shape and
+    prediction dtype launches, with the branch of the launch plan ("rows": R <= 1,024, one thread
+    per row; "strided" above).  Host only."""
+    R, C, D = _bd_shape("box_head_detections_kernel", R, C, detections_per_img)
+    lib = _lib.load(require_gpu=False)
+    buf = _lib.ctypes.create_string_buffer(256)
+    _lib.check(lib.frcnn_box_detections_kernel(_lib.dtype_code(dtype), R, C, D, buf, 256), "box_detections_kernel")
+    return buf.value.decode()
+
+
+def box_head_detections(class_logits, box_regression, proposals, prop_count, image_sizes, *, score_thresh: float = 0.05,
+                        nms_thresh: float = 0.5, detections_per_img: int = 100, min_size: float = 1e-2,
+                        reg_weights=(10.0, 10.0, 5.0, 5.0), original_sizes=None, out=None, workspace=None):
+    """The inference half of a box head on the pyramid path: torchvision's
+    ``RoIHeads.postprocess_detections`` (softmax, ``BoxCoder(reg_weights).decode``,
+    ``clip_boxes_to_image``, ``score_thresh``, ``remove_small_boxes(min_size)``, class-wise NMS,
+    the best ``detections_per_img`` by score) and, with ``original_sizes``,
+    ``GeneralizedRCNNTransform.postprocess``'s ``resize_boxes``, for the whole batch: three
+    launches, no host synchronisation (frcnn_box_detections_t; DESIGN.md §3 "Pyramid box-head
+    inference" is the contract).
+
+    ``class_logits`` [N*R, C] and ``box_regression`` [N*R, 4C]: the head's outputs for
+    ``propose_multilevel``'s ``rois`` (row n*R + r is proposal r of image n), both fp32, both
+    float16 or both bfloat16, widened exactly inside the kernels; ``proposals`` fp32 [N, R, 4] of
+    (x1, y1, x2, y2) and ``prop_count`` int32 [N] -- ``propose_multilevel``'s ``boxes`` and
+    ``count`` (clamped; rows past the count are ignored); ``image_sizes``: fp32 device tensor
+    [N, 2] of (h, w), or one host (h, w) for every image; ``original_sizes``: fp32 device tensor
+    [N, 2] of (h, w), or None.
+
+    Returns ``BoxDetections(boxes fp32 [N, D, 4] (padding 0), labels int32 [N, D] (-1), scores fp32
+    [N, D] (0), roi int32 [N, D] (the proposal row; -1), count int32 [N], total int32 [N] (kept
+    before the cut to D))``, an image's detections by (score descending, row, class).  The tuple
+    feeds ``eval_update`` / ``coco_eval_update`` as it is.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device or a strided view raises
+    RuntimeError naming the argument before any launch.  ``out``: the six outputs, caller-owned;
+    ``workspace``: a uint8 device tensor of at least the cached size."""
+    op = "box_head_detections"
+    lib = _lib.load()
+    code = _lib.prediction_dtype_code(op, (("class_logits", class_logits), ("box_regression", box_regression)))
+    if not isinstance(proposals, torch.Tensor) or proposals.dim() != 3:
+        raise RuntimeError(f"{op}: proposals must be an fp32 device tensor of shape [N, R, 4]")
+    N = int(proposals.shape[0])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: proposals: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if class_logits.dim() != 2:
+        raise RuntimeError(f"{op}: class_logits must be a device tensor of shape [N*R, C]; got {list(class_logits.shape)}")
+    R, C, D = _bd_shape(op, proposals.shape[1], class_logits.shape[1], detections_per_img)
+    dev = _rpnt_device(op, "class_logits", class_logits)
+    dt = class_logits.dtype
+    _rpnt_tensor(op, "class_logits", class_logits, dt, (N * R, C), dev)
+    _rpnt_tensor(op, "box_regression", box_regression, dt, (N * R, 4 * C), dev)
+    _rpnt_tensor(op, "proposals", proposals, torch.float32, (N, R, 4), dev)
+    _rpnt_tensor(op, "prop_count", prop_count, torch.int32, (N,), dev)
+    if isinstance(image_sizes, torch.Tensor):
+        _rpnt_tensor(op, "image_sizes", image_sizes, torch.float32, (N, 2), dev)
+        sizes = image_sizes
+    else:
+        try:
+            hw = (float(image_sizes[0]), float(image_sizes[1]))
+            if len(image_sizes) != 2:
+                raise ValueError
+        except (TypeError, ValueError, IndexError):
+            raise RuntimeError(f"{op}: image_sizes must be an fp32 device tensor [N, 2] of (h, w) or one host "
+                               f"(h, w); got {image_sizes!r}") from None
+        skey = (hw, N, dev.index)
+        sizes = _fpn_sizes_cache.get(skey)
+        if sizes is None:
+            sizes = torch.tensor([hw] * N, dtype=torch.float32).to(dev)
+            _fpn_sizes_cache[skey] = sizes
+    if original_sizes is not None:
+        _rpnt_tensor(op, "original_sizes", original_sizes, torch.float32, (N, 2), dev)
+    try:
+        wts = tuple(float(w) for w in reg_weights)
+    except (TypeError, ValueError):
+        wts = ()
+    if len(wts) != 4 or not all(0.0 < w < float("inf") for w in wts):
+        raise RuntimeError(f"{op}: reg_weights must be four finite positive numbers; got {reg_weights!r}")
+    need = _bd_ws.get((N, R, C))
+    if need is None:
+        need = int(lib.frcnn_box_detections_workspace_size(N, R, C))
+        if need == 0:
+            raise RuntimeError(f"{op}: {lib.frcnn_last_error().decode()}")
+        _bd_ws[(N, R, C)] = need
+    i32, f32 = torch.int32, torch.float32
+    shapes = (((N, D, 4), f32, "boxes"), ((N, D), i32, "labels"), ((N, D), f32, "scores"), ((N, D), i32, "roi"),
+              ((N,), i32, "count"), ((N,), i32, "total"))
+    if out is None:
+        outs = tuple(torch.empty(s, dtype=d, device=dev) for s, d, _ in shapes)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != 6:
+            raise RuntimeError(f"{op}: out must be the six outputs (boxes, labels, scores, roi, count, total)")
+        outs = tuple(out)
+        for i, (s, d, nm) in enumerate(shapes):
+            _rpnt_tensor(op, f"out[{i}] ({nm})", outs[i], d, s, dev)
+    ws = workspace if workspace is not None else _lib.cached_workspace(op, need, dev)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous()
+            or ws.numel() < need or ws.device != dev):
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 tensor of at least {need} B on {dev}")
+    _lib.check(lib.frcnn_box_detections_t(code, N, R, C, _lib.ptr(class_logits), _lib.ptr(box_regression),
+                                          _lib.ptr(proposals), _lib.ptr(prop_count), _lib.ptr(sizes),
+                                          _lib.ptr(original_sizes), float(score_thresh), float(nms_thresh), D,
+                                          float(min_size), *wts, *[_lib.ptr(t) for t in outs], _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr()), op)
+    return BoxDetections(*outs)
 
 
 # ----------------------------------------------------------------- detections
