@@ -618,6 +618,65 @@ int frcnn_box_detections_t(int dtype, int N, int R, int C, const void* class_log
  * "bd_score_kernel<ElemF32> bd_class_nms_kernel<ElemF32,1>[rows] bd_merge_kernel<ElemF32>". */
 int frcnn_box_detections_kernel(int dtype, int R, int C, int detections_per_img, char* name, size_t len);
 
+/* Pyramid mask head (DESIGN.md §3 "Pyramid mask head" is the contract): torchvision's
+ * project_masks_on_boxes, maskrcnn_loss, and maskrcnn_inference + paste_masks_in_image for a
+ * whole batch.  No host synchronisation, no floating-point atomics, every output element stored
+ * exactly once per call, the same bits on every call; fp32 with every operation rounded
+ * separately, '/' and exp correctly rounded.
+ *
+ * frcnn_mask_targets: two launches.  bt_rois fp32 [N*B,5], bt_labels / bt_matched int32 [N,B]:
+ *   rois, labels, matched of frcnn_box_head_targets; gt_masks uint8 [N,G,Hm,Wm], a byte v read
+ *   as the fp32 value v.  An image's positives (label >= 1) go in slot order to rows 0..count-1
+ *   of its P rows, count[n] = min(positives, P): rois fp32 [N*P,5] = (n, box), labels, matched,
+ *   slot (the source slot) int32 [N,P]; the rows behind them are (-1,0,0,0,0) and -1.
+ *   targets fp32 [N*P,M,M]: row = RoIAlign of plane (n, matched) over the box with
+ *   spatial_scale 1, sampling_ratio -1, aligned = false, in frcnn_roi_align_fwd_t's order of
+ *   operations (iy outer, ix inner, w1*v1 + w2*v2 + w3*v3 + w4*v4 left to right, one division
+ *   by the sample count); +0 for a padding row, a matched outside [0,G), or a coordinate that
+ *   is NaN or beyond 2^20 in magnitude.
+ *   Limits: N in [1,1024], B and P in [1,1024], G in [1,256], Hm, Wm in [1,4096], M in [1,56].
+ * frcnn_mask_losses_fwd_t / _bwd_t: mask_logits `dtype` [N*P,C,M,M], read in place; targets,
+ *   labels, count as frcnn_mask_targets wrote them.  A row below its image's count contributes
+ *   channel labels[row] only: l = (max(x,0) - x*t) + log1p(exp(-|x|)) in fp32 per element (exp
+ *   and log1p correctly rounded), summed in fp64 in a fixed order; loss[0] = sum / (S*M*M)
+ *   rounded once, S = the sum of the counts (+0 for S == 0); a row whose label is outside
+ *   [0,C) is skipped and counted; stats = (S, skipped, 0, 0).
+ *   Backward: every element of dlogits stored once in `dtype` with 16-byte stores:
+ *   (1/(1+exp(-x)) - t) * (*g_loss / (float)(S*M*M)) on the labelled channel of such a row, +0
+ *   elsewhere; g_loss is a device pointer, NULL gives zeros.  dlogits 16-byte aligned.
+ *   Limits: C in [2,128]; the workspace is stream-ordered scratch, 256-byte aligned.
+ * frcnn_mask_paste_t: one launch.  mask_logits `dtype` [N*D,C,M,M]; boxes fp32 [N,D,4], labels
+ *   int32 [N,D], count int32 [N] of frcnn_box_detections_t; image_sizes / original_sizes fp32
+ *   [N,2] of (h,w) or NULL (image_sizes needs original_sizes: the boxes are then multiplied by
+ *   orig / image as frcnn_box_detections_t does it; original_sizes alone only clips).  Per
+ *   detection: p = 1/(1+exp(-x)) of channel label, zero-padded by `padding` to S = M + 2*padding;
+ *   expand_boxes with the fp32 scale S/M; truncation toward zero; w = max(x2-x1+1, 1), h alike;
+ *   ATen's bilinear formula (align_corners = false): scale = (float)S/(float)w, src = scale*(d+0.5)
+ *   - 0.5 clamped below at 0, i0 = (int)src, i1 = i0 + (i0 < S-1), l1 = src - i0, l0 = 1 - l1,
+ *   value = l0y*(l0x*a + l1x*b) + l1y*(l0x*c + l1x*d); written inside [0,im_w) x [0,im_h), zeros
+ *   elsewhere.  masks uint8 [N,D,Hc,Wc] of (value > threshold) when `binary`, else fp32 values.
+ *   All zeros: a row at or beyond count, a label outside [1,C), an inverted box, a coordinate
+ *   (before or after the expansion) that is NaN or beyond 2^20 in magnitude.
+ *   Limits: D in [1,1024], padding in [0,4], Hc, Wc in [1,4096], M in [1,56].
+ * The *_kernel queries are host only and name the kernels and the plan branch a call reaches. */
+int frcnn_mask_targets(int N, int B, int P, int G, int Hm, int Wm, int M, const float* bt_rois,
+                       const int32_t* bt_labels, const int32_t* bt_matched, const uint8_t* gt_masks, float* rois,
+                       int32_t* labels, int32_t* matched, int32_t* slot, int32_t* count, float* targets, void* stream);
+int frcnn_mask_targets_kernel(int B, int P, int M, char* name, size_t len);
+size_t frcnn_mask_losses_workspace_size(int N, int P);
+int frcnn_mask_losses_fwd_t(int dtype, int N, int P, int C, int M, const void* mask_logits, const float* targets,
+                            const int32_t* labels, const int32_t* count, float* loss, int32_t* stats, void* workspace,
+                            size_t ws_bytes, void* stream);
+int frcnn_mask_losses_bwd_t(int dtype, int N, int P, int C, int M, const void* mask_logits, const float* targets,
+                            const int32_t* labels, const int32_t* count, const int32_t* stats, const float* g_loss,
+                            void* dlogits, void* stream);
+int frcnn_mask_losses_kernel(int dtype, int C, int M, char* name, size_t len);
+int frcnn_mask_paste_t(int dtype, int N, int D, int C, int M, const void* mask_logits, const float* boxes,
+                       const int32_t* labels, const int32_t* count, const float* image_sizes,
+                       const float* original_sizes, int padding, float threshold, int binary, int Hc, int Wc,
+                       void* masks, void* stream);
+int frcnn_mask_paste_kernel(int dtype, int M, int padding, int Wc, int binary, char* name, size_t len);
+
 /* --------------------------------------------------------- target creators */
 
 /* utils/utils.py:102 bbox_iou(bbox_a, bbox_b) -> [na, nb], with numpy's dtype

@@ -105,6 +105,14 @@ SIGNATURES = {
     "frcnn_box_detections_t": (I32, [I32, I32, I32, I32, P, P, P, P, P, P, F32, F64, I32, F32, F32, F32, F32, F32,
                                      P, P, P, P, P, P, P, SZ, P]),
     "frcnn_box_detections_kernel": (I32, [I32, I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_mask_targets": (I32, [I32, I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
+    "frcnn_mask_targets_kernel": (I32, [I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_mask_losses_workspace_size": (SZ, [I32, I32]),
+    "frcnn_mask_losses_fwd_t": (I32, [I32, I32, I32, I32, I32, P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_mask_losses_bwd_t": (I32, [I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P]),
+    "frcnn_mask_losses_kernel": (I32, [I32, I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_mask_paste_t": (I32, [I32, I32, I32, I32, I32, P, P, P, P, P, P, I32, F32, I32, I32, I32, P, P]),
+    "frcnn_mask_paste_kernel": (I32, [I32, I32, I32, I32, I32, ctypes.c_char_p, SZ]),
     "frcnn_bbox_iou": (I32, [P, I32, I64, P, I32, I64, P, P]),
     "frcnn_bbox2reg": (I32, [P, I32, P, I32, I64, P, P]),
     "frcnn_anchor_target_workspace_size": (SZ, [I32, I32, I32]),

@@ -19,8 +19,11 @@ then RoIAlign forward and its deterministic HIP backward (DESIGN.md §3
 ``RoIHeads.select_training_samples`` and ``fastrcnn_loss``; DESIGN.md §3 "Pyramid box-head
 training").  ``BoxHeadDetections`` is the inference half: torchvision's
 ``RoIHeads.postprocess_detections`` and the transform's ``resize_boxes`` on
-``ops.box_head_detections`` (DESIGN.md §3 "Pyramid box-head inference").  Both stand beside
-``ResnetHead``; neither they nor the pyramid ops are wired into ``FasterRCNN``.
+``ops.box_head_detections`` (DESIGN.md §3 "Pyramid box-head inference").  ``MaskHeadTraining`` and
+``MaskHeadInference`` are the mask head of the same ``RoIHeads`` (``project_masks_on_boxes``,
+``maskrcnn_loss``, ``maskrcnn_inference`` + ``paste_masks_in_image``; DESIGN.md §3 "Pyramid mask
+head").  All stand beside ``ResnetHead``; neither they nor the pyramid ops are wired into
+``FasterRCNN``.
 """
 from __future__ import annotations
 
@@ -144,3 +147,48 @@ class BoxHeadDetections(nn.Module):
                                        score_thresh=self.score_thresh, nms_thresh=self.nms_thresh,
                                        detections_per_img=self.detections_per_img, min_size=self.min_size,
                                        reg_weights=self.reg_weights, original_sizes=original_sizes)
+
+
+class MaskHeadTraining(nn.Module):
+    """The training half of torchvision's ``RoIHeads`` for a mask head on pooled pyramid features:
+    the positives of the box head's sample with ``project_masks_on_boxes`` on
+    ``ops.mask_head_targets`` and ``maskrcnn_loss`` on ``ops.mask_head_losses`` (DESIGN.md §3
+    "Pyramid mask head"); nothing synchronises.
+
+    ``targets(...).rois`` feeds ``ops.multiscale_roi_align`` as it is; the head's logits for those
+    rows go to ``losses``.  ``positives_per_image``: the rows kept per image (default: every slot;
+    a sampler with ``positive_fraction`` f never yields more than ``int(B * f)``)."""
+
+    def __init__(self, mask_size=28, positives_per_image=None):
+        super().__init__()
+        self.mask_size = mask_size
+        self.positives_per_image = positives_per_image
+
+    def targets(self, box_targets, gt_masks):
+        """-> ``ops.MaskHeadTargets``.  ``box_targets``: the ``ops.BoxHeadTargets`` of the box head;
+        ``gt_masks``: uint8 device tensor [N, G, Hm, Wm]."""
+        return ops.mask_head_targets(box_targets, gt_masks, mask_size=self.mask_size,
+                                     positives_per_image=self.positives_per_image)
+
+    def losses(self, mask_logits, targets):
+        """-> the mask loss of the head's logits [N*P, C, M, M] for ``targets.rois``."""
+        return ops.mask_head_losses(mask_logits, targets)
+
+
+class MaskHeadInference(nn.Module):
+    """The inference half: torchvision's ``maskrcnn_inference`` and ``paste_masks_in_image`` on
+    ``ops.mask_head_paste``; nothing synchronises.  ``ops.detection_rois(detections)`` gives the
+    RoIs to pool the mask features for."""
+
+    def __init__(self, padding=1, threshold=0.5):
+        super().__init__()
+        self.padding = padding
+        self.threshold = threshold
+
+    def forward(self, mask_logits, detections, canvas_size, image_sizes=None, original_sizes=None):
+        """-> masks [N, D, Hc, Wc] (uint8 0 / 1, or fp32 probabilities with ``threshold=None``).
+        ``mask_logits`` [N*D, C, M, M]: the head's outputs for ``ops.detection_rois(detections)``;
+        ``detections``: the ``ops.BoxDetections`` of the box head."""
+        return ops.mask_head_paste(mask_logits, detections.boxes, detections.labels, detections.count, canvas_size,
+                                   image_sizes=image_sizes, original_sizes=original_sizes, padding=self.padding,
+                                   threshold=self.threshold)

@@ -1622,6 +1622,288 @@ def box_head_detections(class_logits, box_regression, proposals, prop_count, ima
     return BoxDetections(*outs)
 
 
+# ------------------------------------------------------- pyramid mask head
+MASK_HEAD_MAX_M, MASK_HEAD_MAX_G, MASK_HEAD_MAX_DIM, MASK_HEAD_MAX_PAD = 56, 256, 4096, 4
+MaskHeadTargets = collections.namedtuple("MaskHeadTargets", "rois labels matched slot count targets")
+_mhl_ws = {}   # (N, P) -> workspace bytes of the losses' forward
+
+
+def _mh_name(fn, what, *args) -> str:
+    buf = _lib.ctypes.create_string_buffer(256)
+    _lib.check(fn(*args, buf, 256), what)
+    return buf.value.decode()
+
+
+def mask_head_targets_kernel(B, positives_per_image=None, mask_size=28) -> str:
+    """frcnn_mask_targets_kernel: the two kernels a ``mask_head_targets`` call launches and the
+    plan branch of the second ("one": M * M <= 256, a thread owns at most one bin; "strided"
+    above).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    P = int(B if positives_per_image is None else positives_per_image)
+    return _mh_name(lib.frcnn_mask_targets_kernel, "mask_targets_kernel", int(B), P, int(mask_size))
+
+
+def mask_head_losses_kernel(C, mask_size=28, dtype=torch.float32) -> str:
+    """frcnn_mask_losses_kernel: the forward's two kernels and the backward's, with the elements
+    of its 16-byte stores.  Host only."""
+    lib = _lib.load(require_gpu=False)
+    return _mh_name(lib.frcnn_mask_losses_kernel, "mask_losses_kernel", _lib.dtype_code(dtype), int(C), int(mask_size))
+
+
+def mask_head_paste_kernel(mask_size, canvas_w, padding=1, threshold=0.5, dtype=torch.float32) -> str:
+    """frcnn_mask_paste_kernel: the paste kernel of this logit dtype and output form ("u8" with a
+    threshold, "f32" with ``threshold=None``) and its plan branch ("vec16" / "vec4": every row of
+    the canvas is whole vectors; "+edges": rows have an unaligned head or a tail).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    return _mh_name(lib.frcnn_mask_paste_kernel, "mask_paste_kernel", _lib.dtype_code(dtype), int(mask_size),
+                    int(padding), int(canvas_w), int(threshold is not None))
+
+
+def mask_head_targets(box_targets, gt_masks, *, mask_size: int = 28, positives_per_image=None, out=None):
+    """The mask targets of torchvision's ``RoIHeads.forward`` / ``project_masks_on_boxes`` for the
+    whole batch: two launches, no host synchronisation (frcnn_mask_targets; DESIGN.md §3 "Pyramid
+    mask head" is the contract).
+
+    ``box_targets``: the ``BoxHeadTargets`` of ``box_head_targets`` (B slots per image);
+    ``gt_masks``: uint8 device tensor [N, G, Hm, Wm], read as it is (a byte v is the value v).
+    An image's positives (``labels >= 1``) are compacted in slot order into rows 0..count-1 of
+    its ``P = positives_per_image`` rows (default B); positives beyond P are dropped.
+
+    Returns ``MaskHeadTargets(rois fp32 [N*P, 5], labels, matched, slot int32 [N, P], count int32
+    [N], targets fp32 [N*P, M, M])``: ``targets[row]`` is ``roi_align`` of the matched mask over
+    the row's box at ``(M, M)`` with ``spatial_scale=1``, ``sampling_ratio=-1``, ``aligned=False``,
+    bit for bit; a ``matched`` outside [0, G) or a box that is not finite gives zeros.  Padding
+    rows: ``rois`` (-1, 0, 0, 0, 0), labels / matched / slot -1, targets +0.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device or a strided view raises
+    RuntimeError naming the argument before any launch.  ``out``: the six outputs, caller-owned."""
+    op = "mask_head_targets"
+    lib = _lib.load()
+    if not isinstance(box_targets, BoxHeadTargets):
+        raise RuntimeError(f"{op}: box_targets must be the BoxHeadTargets of box_head_targets; got "
+                           f"{type(box_targets).__name__}")
+    lab = box_targets.labels
+    if not isinstance(lab, torch.Tensor) or lab.dim() != 2:
+        raise RuntimeError(f"{op}: box_targets.labels must be an int32 device tensor of shape [N, B]")
+    N, B = int(lab.shape[0]), int(lab.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: box_targets.labels: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= B <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: box_targets.labels: B must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {B}")
+    dev = _rpnt_device(op, "box_targets.labels", lab)
+    _rpnt_tensor(op, "box_targets.labels", lab, torch.int32, (N, B), dev)
+    _rpnt_tensor(op, "box_targets.matched", box_targets.matched, torch.int32, (N, B), dev)
+    _rpnt_tensor(op, "box_targets.rois", box_targets.rois, torch.float32, (N * B, 5), dev)
+    if not isinstance(gt_masks, torch.Tensor) or gt_masks.dim() != 4:
+        raise RuntimeError(f"{op}: gt_masks must be a uint8 device tensor of shape [N, G, Hm, Wm]")
+    G, Hm, Wm = (int(v) for v in gt_masks.shape[1:])
+    if not 1 <= G <= MASK_HEAD_MAX_G:
+        raise RuntimeError(f"{op}: gt_masks: G must be in [1, {MASK_HEAD_MAX_G}]; got {G}")
+    if not (1 <= Hm <= MASK_HEAD_MAX_DIM and 1 <= Wm <= MASK_HEAD_MAX_DIM):
+        raise RuntimeError(f"{op}: gt_masks: Hm and Wm must be in [1, {MASK_HEAD_MAX_DIM}]; got {Hm} x {Wm}")
+    _rpnt_tensor(op, "gt_masks", gt_masks, torch.uint8, (N, G, Hm, Wm), dev)
+    M = int(mask_size)
+    if not 1 <= M <= MASK_HEAD_MAX_M:
+        raise RuntimeError(f"{op}: mask_size must be in [1, {MASK_HEAD_MAX_M}]; got {M}")
+    P = B if positives_per_image is None else int(positives_per_image)
+    if not 1 <= P <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: positives_per_image must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {P}")
+    i32, f32 = torch.int32, torch.float32
+    shapes = (((N * P, 5), f32, "rois"), ((N, P), i32, "labels"), ((N, P), i32, "matched"), ((N, P), i32, "slot"),
+              ((N,), i32, "count"), ((N * P, M, M), f32, "targets"))
+    if out is None:
+        outs = tuple(torch.empty(s, dtype=d, device=dev) for s, d, _ in shapes)
+    else:
+        if not isinstance(out, (list, tuple)) or len(out) != 6:
+            raise RuntimeError(f"{op}: out must be the six outputs (rois, labels, matched, slot, count, targets)")
+        outs = tuple(out)
+        for i, (s, d, nm) in enumerate(shapes):
+            _rpnt_tensor(op, f"out[{i}] ({nm})", outs[i], d, s, dev)
+    _lib.check(lib.frcnn_mask_targets(N, B, P, G, Hm, Wm, M, _lib.ptr(box_targets.rois), _lib.ptr(lab),
+                                      _lib.ptr(box_targets.matched), _lib.ptr(gt_masks),
+                                      *[_lib.ptr(t) for t in outs], _lib.stream_ptr()), op)
+    return MaskHeadTargets(*outs)
+
+
+class _MaskHeadLossesFunction(torch.autograd.Function):
+    """frcnn_mask_losses_fwd_t / _bwd_t; the incoming gradient goes to the kernel as a device pointer."""
+
+    @staticmethod
+    def forward(ctx, targets, code, ws, logits):
+        lib = _lib.load()
+        N, P = targets.labels.shape
+        C, M = int(logits.shape[1]), int(logits.shape[2])
+        dev = logits.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        stats = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.frcnn_mask_losses_fwd_t(code, N, P, C, M, _lib.ptr(logits), _lib.ptr(targets.targets),
+                                               _lib.ptr(targets.labels), _lib.ptr(targets.count), _lib.ptr(loss),
+                                               _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "mask_head_losses forward")
+        ctx.save_for_backward(logits, targets.targets, targets.labels, targets.count, stats)
+        ctx.meta = (code, N, P, C, M)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(stats)
+        return loss[0], stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_stats):
+        lib = _lib.load()
+        code, N, P, C, M = ctx.meta
+        logits, tgt, labels, count, stats = ctx.saved_tensors
+        if g is not None and (g.dtype != torch.float32 or not g.is_cuda or g.numel() != 1):
+            raise RuntimeError("mask_head_losses backward: the gradient of the loss must be one torch.float32 on "
+                               f"the device; got {g.dtype} on {g.device.type} with {g.numel()} elements")
+        d = torch.empty_like(logits)   # each element is stored once
+        _lib.check(lib.frcnn_mask_losses_bwd_t(code, N, P, C, M, _lib.ptr(logits), _lib.ptr(tgt), _lib.ptr(labels),
+                                               _lib.ptr(count), _lib.ptr(stats), _lib.ptr(g), _lib.ptr(d),
+                                               _lib.stream_ptr()), "mask_head_losses backward")
+        return None, None, None, d
+
+
+def _mask_head_losses(mask_logits, targets, workspace):
+    op = "mask_head_losses"
+    lib = _lib.load()
+    if not isinstance(targets, MaskHeadTargets):
+        raise RuntimeError(f"{op}: targets must be the MaskHeadTargets of mask_head_targets; got {type(targets).__name__}")
+    code = _lib.prediction_dtype_code(op, (("mask_logits", mask_logits),))
+    if mask_logits.dim() != 4:
+        raise RuntimeError(f"{op}: mask_logits must be a device tensor of shape [N*P, C, M, M]; got "
+                           f"{list(mask_logits.shape)}")
+    C, M = int(mask_logits.shape[1]), int(mask_logits.shape[2])
+    if not 2 <= C <= BOX_HEAD_MAX_C:
+        raise RuntimeError(f"{op}: mask_logits: C must be in [2, {BOX_HEAD_MAX_C}]; got {C}")
+    if not 1 <= M <= MASK_HEAD_MAX_M:
+        raise RuntimeError(f"{op}: mask_logits: M must be in [1, {MASK_HEAD_MAX_M}]; got {M}")
+    dev = _rpnt_device(op, "mask_logits", mask_logits)
+    if not isinstance(targets.labels, torch.Tensor) or targets.labels.dim() != 2:
+        raise RuntimeError(f"{op}: targets.labels must be an int32 device tensor of shape [N, P]")
+    N, P = int(targets.labels.shape[0]), int(targets.labels.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: targets.labels: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= P <= RPN_TARGETS_MAX_BATCH:
+        raise RuntimeError(f"{op}: targets.labels: P must be in [1, {RPN_TARGETS_MAX_BATCH}]; got {P}")
+    _rpnt_tensor(op, "mask_logits", mask_logits, mask_logits.dtype, (N * P, C, M, M), dev)
+    _rpnt_tensor(op, "targets.labels", targets.labels, torch.int32, (N, P), dev)
+    _rpnt_tensor(op, "targets.count", targets.count, torch.int32, (N,), dev)
+    _rpnt_tensor(op, "targets.targets", targets.targets, torch.float32, (N * P, M, M), dev)
+    need = _mhl_ws.get((N, P))
+    if need is None:
+        need = _mhl_ws[(N, P)] = int(lib.frcnn_mask_losses_workspace_size(N, P))
+    ws = workspace if workspace is not None else _lib.cached_workspace(op, need, dev)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous()
+            or ws.numel() < need or ws.device != dev):
+        raise RuntimeError(f"{op}: workspace must be a contiguous uint8 tensor of at least {need} B on {dev}")
+    return _MaskHeadLossesFunction.apply(targets, code, ws, mask_logits)
+
+
+def mask_head_losses(mask_logits, targets, *, workspace=None):
+    """torchvision's ``maskrcnn_loss`` on ``mask_head_targets``' result, differentiable in
+    ``mask_logits`` (frcnn_mask_losses_fwd_t / _bwd_t; DESIGN.md §3 "Pyramid mask head").
+
+    ``mask_logits``: [N*P, C, M, M] in fp32, float16 or bfloat16, contiguous, row ``n*P + r`` as
+    ``targets.rois`` orders them; only channel ``labels[row]`` of the rows below their image's
+    ``count`` is read.  Returns the 0-dim fp32 mean over the S*M*M elements of the
+    binary cross-entropy with logits against the soft targets, S the sum of ``count`` taken on
+    the device; S == 0 gives +0 and all-zero gradients.  A row whose label is >= C is skipped
+    and counted (``mask_head_losses_with_stats``), never used as an index.
+
+    The backward stores every element of the gradient once, in the input's dtype, with no
+    atomics: the same bits on every call.  Nothing is converted and nothing synchronises; a wrong
+    dtype, shape, device or a strided view raises RuntimeError naming the argument before any
+    launch.  ``workspace``: a uint8 device tensor of at least the cached size."""
+    return _mask_head_losses(mask_logits, targets, workspace)[0]
+
+
+def mask_head_losses_with_stats(mask_logits, targets, *, workspace=None):
+    """``mask_head_losses`` plus ``stats``: int32 device tensor (S, rows skipped for a label
+    outside [0, C), 0, 0)."""
+    return _mask_head_losses(mask_logits, targets, workspace)
+
+
+def mask_head_paste(mask_logits, boxes, labels, count, canvas_size, *, image_sizes=None, original_sizes=None,
+                    padding: int = 1, threshold=0.5, out=None):
+    """torchvision's ``maskrcnn_inference`` and ``paste_masks_in_image`` for the whole batch: one
+    launch, no host synchronisation (frcnn_mask_paste_t; DESIGN.md §3 "Pyramid mask head").
+
+    ``mask_logits``: [N*D, C, M, M] in fp32, float16 or bfloat16; ``boxes`` fp32 [N, D, 4],
+    ``labels`` int32 [N, D], ``count`` int32 [N]: those of ``BoxDetections``;
+    ``canvas_size = (Hc, Wc)``: host ints.  ``original_sizes`` (fp32 device [N, 2] of (h, w)) clips
+    each image's masks to its own size; with ``image_sizes`` as well the boxes are first mapped by
+    ``resize_boxes`` as ``box_head_detections`` does it.
+
+    Returns ``masks [N, D, Hc, Wc]``: uint8 0 / 1 of ``prob > threshold``, or the fp32
+    probabilities with ``threshold=None``.  Rows at or beyond ``count``, labels outside [1, C),
+    boxes that are not finite or are inverted give all-zero masks.  ``out``: the caller's tensor."""
+    op = "mask_head_paste"
+    lib = _lib.load()
+    code = _lib.prediction_dtype_code(op, (("mask_logits", mask_logits),))
+    if mask_logits.dim() != 4:
+        raise RuntimeError(f"{op}: mask_logits must be a device tensor of shape [N*D, C, M, M]; got "
+                           f"{list(mask_logits.shape)}")
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3:
+        raise RuntimeError(f"{op}: boxes must be an fp32 device tensor of shape [N, D, 4]")
+    N, D = int(boxes.shape[0]), int(boxes.shape[1])
+    if not 1 <= N <= FPN_MAX_N:
+        raise RuntimeError(f"{op}: boxes: N must be in [1, {FPN_MAX_N}]; got {N}")
+    if not 1 <= D <= BOX_DET_MAX_D:
+        raise RuntimeError(f"{op}: boxes: D must be in [1, {BOX_DET_MAX_D}]; got {D}")
+    C, M = int(mask_logits.shape[1]), int(mask_logits.shape[2])
+    if not 2 <= C <= BOX_HEAD_MAX_C:
+        raise RuntimeError(f"{op}: mask_logits: C must be in [2, {BOX_HEAD_MAX_C}]; got {C}")
+    if not 1 <= M <= MASK_HEAD_MAX_M:
+        raise RuntimeError(f"{op}: mask_logits: M must be in [1, {MASK_HEAD_MAX_M}]; got {M}")
+    dev = _rpnt_device(op, "mask_logits", mask_logits)
+    _rpnt_tensor(op, "mask_logits", mask_logits, mask_logits.dtype, (N * D, C, M, M), dev)
+    _rpnt_tensor(op, "boxes", boxes, torch.float32, (N, D, 4), dev)
+    _rpnt_tensor(op, "labels", labels, torch.int32, (N, D), dev)
+    _rpnt_tensor(op, "count", count, torch.int32, (N,), dev)
+    try:
+        Hc, Wc = int(canvas_size[0]), int(canvas_size[1])
+        if len(canvas_size) != 2:
+            raise ValueError
+    except (TypeError, ValueError, IndexError):
+        raise RuntimeError(f"{op}: canvas_size must be two host ints (Hc, Wc); got {canvas_size!r}") from None
+    if not (1 <= Hc <= MASK_HEAD_MAX_DIM and 1 <= Wc <= MASK_HEAD_MAX_DIM):
+        raise RuntimeError(f"{op}: canvas_size: Hc and Wc must be in [1, {MASK_HEAD_MAX_DIM}]; got {Hc} x {Wc}")
+    if original_sizes is not None:
+        _rpnt_tensor(op, "original_sizes", original_sizes, torch.float32, (N, 2), dev)
+    if image_sizes is not None:
+        if original_sizes is None:
+            raise RuntimeError(f"{op}: image_sizes maps the boxes to original_sizes, which is missing")
+        _rpnt_tensor(op, "image_sizes", image_sizes, torch.float32, (N, 2), dev)
+    pad = int(padding)
+    if not 0 <= pad <= MASK_HEAD_MAX_PAD:
+        raise RuntimeError(f"{op}: padding must be in [0, {MASK_HEAD_MAX_PAD}]; got {pad}")
+    binary = threshold is not None
+    thr = float(threshold) if binary else 0.0
+    if thr != thr:
+        raise RuntimeError(f"{op}: threshold must be a number or None; got {threshold!r}")
+    odt = torch.uint8 if binary else torch.float32
+    if out is None:
+        out = torch.empty((N, D, Hc, Wc), dtype=odt, device=dev)
+    else:
+        _rpnt_tensor(op, "out", out, odt, (N, D, Hc, Wc), dev)
+    _lib.check(lib.frcnn_mask_paste_t(code, N, D, C, M, _lib.ptr(mask_logits), _lib.ptr(boxes), _lib.ptr(labels),
+                                      _lib.ptr(count), _lib.ptr(image_sizes), _lib.ptr(original_sizes), pad, thr,
+                                      int(binary), Hc, Wc, _lib.ptr(out), _lib.stream_ptr()), op)
+    return out
+
+
+def detection_rois(detections):
+    """``[N*D, 5]`` RoIs (n, x1, y1, x2, y2) of a ``BoxDetections`` for ``multiscale_roi_align``;
+    the rows at or beyond ``count`` are the padding (-1, 0, 0, 0, 0), which it pools to zeros.
+    Plain torch ops, no synchronisation."""
+    boxes, count = detections.boxes, detections.count
+    N, D = int(boxes.shape[0]), int(boxes.shape[1])
+    real = torch.arange(D, device=boxes.device)[None, :] < count[:, None]
+    idx = torch.arange(N, device=boxes.device, dtype=boxes.dtype)[:, None].expand(N, D)
+    idx = torch.where(real, idx, idx.new_full((), -1.0))
+    b = torch.where(real[:, :, None], boxes, boxes.new_zeros(()))
+    return torch.cat([idx[:, :, None], b], 2).reshape(N * D, 5)
+
+
 # ----------------------------------------------------------------- detections
 REG_MEAN =(0.0, 0.0, 0.0, 0.0)   # utils/utils.py:272 (ProposalTargetCreator's normalisation)
 REG_STD = (0.1, 0.1, 0.2, 0.2)
