@@ -872,6 +872,17 @@ int frcnn_eval_ap(int C, int64_t n_records, const int64_t* hdr, const uint64_t* 
                   const int8_t* rec_flag, int use_07_metric, double* ap, double* map,
                   uint64_t* sorted_key, void* ws, size_t ws_bytes, void* stream);
 
+/* The launch shape of the two entry points above for a batch of N images of M
+ * slots and a closing step over n_records records, from the constants and host
+ * functions the launches themselves use.  Host only: no HIP call is made.
+ *   plan[0] images per step of the per-workgroup count sums, plan[1] steps for N
+ *   plan[2] slots per match chunk, plan[3] match chunks for M
+ *   plan[4] keys per sort tile, plan[5] sort tiles for n_records, plan[6] sort passes
+ *   plan[7] histogram words one scan covers, plan[8] the scan's share per thread
+ *   plan[9] records per chunk of the precision / recall walk
+ * N and M within frcnn_eval_update's limits, 0 <= n_records <= 2^24. */
+int frcnn_eval_plan(int N, int M, int64_t n_records, int64_t plan[10]);
+
 /* COCO-style evaluation (DESIGN.md "COCO-style evaluation" is the contract:
  * pycocotools.cocoeval with iouType "bbox", restated; no reference counterpart).
  * One batch is matched at the ten IoU thresholds and the four area ranges and

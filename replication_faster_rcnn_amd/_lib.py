@@ -140,6 +140,7 @@ SIGNATURES = {
     "frcnn_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, F64, I32, P, P, P, P, P]),
     "frcnn_eval_ap_workspace_size": (SZ, [I32, I64]),
     "frcnn_eval_ap": (I32, [I32, I64, P, P, P, I32, P, P, P, P, SZ, P]),
+    "frcnn_eval_plan": (I32, [I32, I32, I64, P]),
     "frcnn_coco_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, P, P, P, P, P]),
     "frcnn_coco_eval_workspace_size": (SZ, [I32, I64]),
     "frcnn_coco_eval_accumulate": (I32, [I32, I64, P, P, P, P, P, P, P, P, P, SZ, P]),
@@ -404,6 +405,19 @@ def preprocess_plan(N, max_hw, out_hw) -> dict:
     check(lib.frcnn_preprocess_plan(int(N), int(max_hw[0]), int(max_hw[1]), int(out_hw[0]), int(out_hw[1]), plan),
           "preprocess_plan")
     return dict(zip(PREPROCESS_PLAN_FIELDS, plan))
+
+
+EVAL_PLAN_FIELDS = ("count_step", "count_steps", "match_chunk", "match_chunks", "sort_tile", "sort_tiles",
+                    "sort_passes", "scan_len", "scan_share", "walk_chunk")
+
+
+def eval_plan(N, M, n_records) -> dict:
+    """frcnn_eval_plan: the chunk, tile and scan numbers ``frcnn_eval_update`` (N images of M
+    slots) and ``frcnn_eval_ap`` (n_records records) launch with, by EVAL_PLAN_FIELDS.  Host only."""
+    lib = load(require_gpu=False)
+    plan = (ctypes.c_int64 * 10)()
+    check(lib.frcnn_eval_plan(int(N), int(M), int(n_records), plan), "eval_plan")
+    return dict(zip(EVAL_PLAN_FIELDS, plan))
 
 
 def set_path(op: str, path) -> None:

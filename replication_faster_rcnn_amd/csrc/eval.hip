@@ -30,6 +30,8 @@
 //                         tp / fp and the suffix maximum of the precision),
 //                         integrating at each record.
 //   eval_map_kernel     : mean of the non-NaN APs in ascending class order.
+//   frcnn_eval_plan     : host only: the chunk, tile and scan numbers of the launches above for
+//                         a shape, from the constants and functions they read (eval_common.h).
 // The limits, the header step, the walk and the sort's host entry
 // (eval_sort_keys) are shared with the COCO-style evaluation (eval_common.h, eval_coco.hip).
 // Integer atomics only (LDS claim minima, npos counts): every result is
@@ -182,15 +184,8 @@ __global__ __launch_bounds__(kEvThreads) void eval_advance_kernel(int N, int M, 
 }
 
 // ----------------------------------------------------------------------- sort
-constexpr int kSortTile = 4096;  // keys per workgroup and pass
-constexpr int kSortBits = 8;
-constexpr int kSortBins = 1 << kSortBits;
-constexpr int kSortFirstBit = 24;  // below it: the insertion order, already ascending in the input
-constexpr int kSortPasses = 5;     // bits 24..63
-constexpr int kScanThreads = 1024;
-
-static int sort_blocks(int64_t n) { return static_cast<int>((n + kSortTile - 1) / kSortTile); }
-
+// The sort's constants, its tile count (ev_sort_blocks) and the scan's share per thread
+// (ev_scan_share) are in eval_common.h.
 // hist[d * nblk + b]: keys of workgroup b's tile with digit d.
 __global__ __launch_bounds__(kEvThreads) void eval_sort_hist_kernel(const uint64_t* __restrict__ in, int n, int shift,
                                                                     int nblk, uint32_t* __restrict__ hist) {
@@ -209,7 +204,7 @@ __global__ __launch_bounds__(kEvThreads) void eval_sort_hist_kernel(const uint64
 __global__ __launch_bounds__(kScanThreads) void eval_sort_scan_kernel(uint32_t* __restrict__ hist, int len) {
     __shared__ uint32_t wsum[kScanThreads / kWave];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int per = (len + kScanThreads - 1) / kScanThreads;
+    const int per = ev_scan_share(len);
     const int lo = min(len, tid * per), hi = min(len, lo + per);
     uint32_t s = 0;
     for (int i = lo; i < hi; ++i) s += hist[i];
@@ -354,7 +349,7 @@ __global__ void eval_map_kernel(int C, const double* __restrict__ ap, double* __
 struct EvalWs {
     uint64_t* a;     // [cap]
     uint64_t* b;     // [cap]
-    uint32_t* hist;  // [kSortBins * sort_blocks(cap)]
+    uint32_t* hist;  // [kSortBins * ev_sort_blocks(cap)]
     size_t bytes;
 };
 
@@ -363,7 +358,7 @@ static EvalWs carve_eval(void* ws, int64_t cap) {
     EvalWs w{};
     w.a = c.take<uint64_t>(static_cast<size_t>(cap));
     w.b = c.take<uint64_t>(static_cast<size_t>(cap));
-    w.hist = c.take<uint32_t>(static_cast<size_t>(kSortBins) * sort_blocks(cap));
+    w.hist = c.take<uint32_t>(static_cast<size_t>(kSortBins) * ev_sort_blocks(cap));
     w.bytes = c.used();
     return w;
 }
@@ -378,14 +373,14 @@ int eval_sort_keys(const uint64_t* rec_key, int64_t n_records, void* ws, size_t 
         set_error("%s: workspace %zu < %zu", who, ws ? ws_bytes : size_t{0}, w.bytes);
         return FRCNN_EWORKSPACE;
     }
-    const int nblk = sort_blocks(n_records);
+    const int nblk = ev_sort_blocks(n_records);
     const uint64_t* src = rec_key;
     uint64_t* dst = w.a;
     for (int pass = 0; pass < kSortPasses; ++pass) {
         const int shift = kSortFirstBit + pass * kSortBits;
         eval_sort_hist_kernel<<<nblk, kEvThreads, 0, st>>>(src, n, shift, nblk, w.hist);
         FRCNN_LAUNCH_CHECK("eval_sort_hist_kernel");
-        eval_sort_scan_kernel<<<1, kScanThreads, 0, st>>>(w.hist, kSortBins * nblk);
+        eval_sort_scan_kernel<<<1, kScanThreads, 0, st>>>(w.hist, ev_scan_len(nblk));
         FRCNN_LAUNCH_CHECK("eval_sort_scan_kernel");
         eval_sort_scatter_kernel<<<nblk, kEvThreads, 0, st>>>(src, dst, n, shift, nblk, w.hist);
         FRCNN_LAUNCH_CHECK("eval_sort_scatter_kernel");
@@ -425,6 +420,27 @@ extern "C" int frcnn_eval_update(int N, int M, int G, int C, int64_t cap, const 
     FRCNN_LAUNCH_CHECK("eval_match_kernel");
     eval_advance_kernel<<<1, kEvThreads, 0, st>>>(N, M, static_cast<long long>(cap), det_count, h);
     FRCNN_LAUNCH_CHECK("eval_advance_kernel");
+    return FRCNN_OK;
+}
+
+extern "C" int frcnn_eval_plan(int N, int M, int64_t n_records, int64_t plan[10]) {
+    FRCNN_REQUIRE(N >= 1 && N <= kEvMaxN, "frcnn_eval_plan: N=%d must be in [1, %d]", N, kEvMaxN);
+    FRCNN_REQUIRE(M >= 1 && M <= kEvMaxM, "frcnn_eval_plan: M=%d must be in [1, %d]", M, kEvMaxM);
+    FRCNN_REQUIRE(n_records >= 0 && n_records <= kEvMaxCap, "frcnn_eval_plan: n_records=%lld must be in [0, %lld]",
+                  static_cast<long long>(n_records), static_cast<long long>(kEvMaxCap));
+    FRCNN_REQUIRE(plan, "frcnn_eval_plan: null plan");
+    const int nblk = ev_sort_blocks(n_records);
+    const int len = ev_scan_len(nblk);
+    plan[0] = kEvThreads;  // images per step of ev_count_sums
+    plan[1] = ev_steps(N);
+    plan[2] = kEvThreads;  // slots per chunk of eval_match_kernel
+    plan[3] = ev_steps(M);
+    plan[4] = kSortTile;
+    plan[5] = nblk;
+    plan[6] = kSortPasses;
+    plan[7] = len;
+    plan[8] = ev_scan_share(len);
+    plan[9] = kEvThreads;  // records per chunk of ev_pr_walk
     return FRCNN_OK;
 }
 

@@ -17,6 +17,23 @@ constexpr int64_t kEvMaxCap = int64_t{1} << 24;  // the record index is a 24-bit
 constexpr int kEvThreads = 256;
 constexpr int kEvWaves = kEvThreads / kWave;
 
+// The sort's shape (eval.hip): the launches, the scan kernel and frcnn_eval_plan read it from here.
+constexpr int kSortTile = 4096;  // keys per workgroup and pass
+constexpr int kSortBits = 8;
+constexpr int kSortBins = 1 << kSortBits;
+constexpr int kSortFirstBit = 24;  // below it: the insertion order, already ascending in the input
+constexpr int kSortPasses = 5;     // bits 24..63
+constexpr int kScanThreads = 1024;
+
+// Sort tiles (workgroups per histogram / scatter launch) of n keys.
+__host__ __device__ inline int ev_sort_blocks(int64_t n) { return static_cast<int>((n + kSortTile - 1) / kSortTile); }
+// Histogram words of one pass, and the contiguous share of them each scan thread takes.
+__host__ __device__ inline int ev_scan_len(int nblk) { return kSortBins * nblk; }
+__host__ __device__ inline int ev_scan_share(int len) { return (len + kScanThreads - 1) / kScanThreads; }
+// Steps of a workgroup's stride loop over n items, kEvThreads at a time (ev_count_sums over the
+// images, eval_match_kernel over an image's slots, ev_pr_walk over a segment's records).
+__host__ __device__ inline int ev_steps(int64_t n) { return static_cast<int>((n + kEvThreads - 1) / kEvThreads); }
+
 __device__ __forceinline__ int ev_count(const int32_t* det_count, int n, int M) {
     const int k = det_count[n];
     return k < 0 ? 0 : (k > M ? M : k);

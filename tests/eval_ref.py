@@ -13,6 +13,18 @@ from replication_faster_rcnn_amd import synth
 
 GARBAGE_BOX, GARBAGE_LABEL, GARBAGE_SCORE = 1e30, 1, 9.0   # slots at or past the count
 
+CHUNK = 256   # records per restart of the two chunk mistakes below: the kernels' workgroup size
+
+# Planted mistakes (``mistake=``): each is one way a kernel could depart from the contract.  tests/eval_cases.py
+# names the case that must tell each of them apart from the contract.
+MATCH_MISTAKES = ("non_strict_threshold", "last_gt_wins_tie", "claim_by_slot", "nan_score_last", "neg_zero_below_zero",
+                  "difficult_consumes", "difficult_in_npos", "plus_one_in_fp32", "invalid_label_is_fp",
+                  "count_not_clamped", "prefix_first_256_images")
+AP_MISTAKES = ("unstable_sort", "envelope_restarts_each_chunk", "envelope_restarts_each_chunk_from_end",
+               "running_sum_restarts_each_chunk", "running_sum_restarts_each_chunk_from_end", "no_division_guard",
+               "empty_class_is_nan", "tenths_by_division")
+MISTAKES = MATCH_MISTAKES + AP_MISTAKES
+
 
 def desc_score_key(s):
     """csrc/common.h desc_score_key: fp32 -> uint32 ascending for descending scores,
@@ -23,21 +35,42 @@ def desc_score_key(s):
     return np.where(np.isnan(s), np.uint32(0), ~asc).astype(np.uint32)
 
 
-def desc_order(s):
+def score_key(s, mistake=None):
+    """desc_score_key, or what a planted mistake makes of it: ``nan_score_last`` gives NaN the
+    largest key, ``neg_zero_below_zero`` leaves -0.0 its own bit pattern's key, just after +0.0's."""
+    s = np.ascontiguousarray(s, np.float32)
+    k = desc_score_key(s)
+    if mistake == "nan_score_last":
+        k = np.where(np.isnan(s), np.uint32(0xFFFFFFFF), k)
+    if mistake == "neg_zero_below_zero":
+        k = np.where(s.view(np.uint32) == np.uint32(0x80000000), np.uint32(0x80000000), k)
+    return k.astype(np.uint32)
+
+
+def desc_order(s, mistake=None):
     """Slots in torch's own stable descending order (NaN first, -0.0 == +0.0,
     ties by slot): the order the devkit loop walks an image's detections in."""
+    if mistake == "claim_by_slot":
+        return list(range(len(s)))
+    if mistake in ("nan_score_last", "neg_zero_below_zero"):
+        return np.argsort(score_key(s, mistake), kind="stable").tolist()
     import torch
     t = torch.from_numpy(np.ascontiguousarray(s, np.float32))
     return torch.sort(t, descending=True, stable=True).indices.numpy().tolist()
 
 
-def iou(a, b, plus_one=1):
+def iou(a, b, plus_one=1, mistake=None):
     """bbox_iou (utils/utils.py:102-119) of one box a against boxes b [g, 4] in
-    fp64, after the pixel convention's +1 on columns 2, 3 of both."""
+    fp64, after the pixel convention's +1 on columns 2, 3 of both.  ``plus_one_in_fp32``
+    adds the detection's +1 before the widening instead of after it."""
+    if plus_one and mistake == "plus_one_in_fp32":
+        a = np.array(a, np.float32)
+        a[2:] = a[2:] + np.float32(1.0)
     a = np.array(a, np.float64).reshape(1, 4)
     b = np.array(b, np.float64).reshape(-1, 4)
     if plus_one:
-        a[:, 2:] = a[:, 2:] + 1.0
+        if mistake != "plus_one_in_fp32":
+            a[:, 2:] = a[:, 2:] + 1.0
         b[:, 2:] = b[:, 2:] + 1.0
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         tl = np.maximum(a[:, None, :2], b[:, :2])
@@ -48,7 +81,8 @@ def iou(a, b, plus_one=1):
         return (area_i / (area_a[:, None] + area_b - area_i))[0]
 
 
-def match_image(boxes, labels, scores, k, gt_boxes, gt_labels, gt_difficult, C, iou_thresh=0.5, plus_one=1):
+def match_image(boxes, labels, scores, k, gt_boxes, gt_labels, gt_difficult, C, iou_thresh=0.5, plus_one=1,
+                mistake=None):
     """The devkit loop on one image.  Returns per slot below k: flag (1 TP, 0
     FP, -1 ignored), record class (0 for a label outside 1..C-1) and the gt the
     slot was matched to (-1: none)."""
@@ -56,22 +90,24 @@ def match_image(boxes, labels, scores, k, gt_boxes, gt_labels, gt_difficult, C, 
     cls = np.zeros(k, np.int64)
     best = np.full(k, -1, np.int64)
     taken = np.zeros(len(gt_labels), bool)
-    for s in desc_order(scores[:k]):
+    for s in desc_order(scores[:k], mistake):
         lab = int(labels[s])
         if not 1 <= lab < C:
-            flag[s] = -1
+            flag[s] = 0 if mistake == "invalid_label_is_fp" else -1
             continue
         cls[s] = lab
         cand = [j for j in range(len(gt_labels)) if int(gt_labels[j]) == lab]
         ovmax, jmax = -np.inf, -1
         if cand:
-            for j, ov in zip(cand, iou(boxes[s], gt_boxes[cand], plus_one)):
-                if ov > ovmax:               # strict: a tie stays with the first gt, a NaN never wins
+            for j, ov in zip(cand, iou(boxes[s], gt_boxes[cand], plus_one, mistake)):
+                # strict: a tie stays with the first gt, a NaN never wins
+                if ov > ovmax or (mistake == "last_gt_wins_tie" and ov >= ovmax):
                     ovmax, jmax = ov, j
-        if ovmax > iou_thresh:
+        if ovmax > iou_thresh or (mistake == "non_strict_threshold" and ovmax >= iou_thresh):
             best[s] = jmax
             if gt_difficult is not None and gt_difficult[jmax]:
-                flag[s] = -1
+                flag[s] = 0 if mistake == "difficult_consumes" and taken[jmax] else -1
+                taken[jmax] = taken[jmax] or mistake == "difficult_consumes"
             elif not taken[jmax]:
                 flag[s] = 1
                 taken[jmax] = True
@@ -92,12 +128,16 @@ class State:
         self.best = []   # per update and image: match_image's matched gt (diagnostics for preconditions)
 
     def update(self, det_boxes, det_labels, det_scores, det_count, gt_boxes, gt_labels, gt_difficult=None,
-               iou_thresh=0.5, plus_one=1):
+               iou_thresh=0.5, plus_one=1, mistake=None):
         N, M = det_labels.shape
         C = self.C
         ks = np.clip(det_count.astype(np.int64), 0, M)
+        # what the positions are derived from: the clamped counts of all N images
+        counted = det_count.astype(np.int64) if mistake == "count_not_clamped" else ks
+        lim = min(N, 256) if mistake == "prefix_first_256_images" else N
         nrec = int(self.hdr[0])
-        if nrec + int(ks.sum()) > self.cap:
+        total = int(counted[:lim].sum())
+        if nrec + total > self.cap:
             self.hdr[2] += 1
             return
         for n in range(N):
@@ -107,25 +147,32 @@ class State:
             gl = np.where(valid, gl, 0)
             gd = None if gt_difficult is None else gt_difficult[n]
             flag, cls, best = match_image(det_boxes[n], det_labels[n], det_scores[n], k, gt_boxes[n], gl, gd, C,
-                                          iou_thresh, plus_one)
+                                          iou_thresh, plus_one, mistake)
             self.best.append(best)
-            idx = nrec + np.arange(k, dtype=np.int64)
+            idx = nrec + int(counted[:min(n, lim)].sum()) + np.arange(k, dtype=np.int64)
             key = (cls.astype(np.uint64) << np.uint64(56)) | \
-                  (desc_score_key(det_scores[n, :k]).astype(np.uint64) << np.uint64(24)) | idx.astype(np.uint64)
-            self.rec_key[nrec:nrec + k] = key
-            self.rec_flag[nrec:nrec + k] = flag
-            self.rec_image[nrec:nrec + k] = self.hdr[1] + n
-            nrec += k
-            pos = valid if gd is None else valid & (np.asarray(gd) == 0)
+                  (score_key(det_scores[n, :k], mistake).astype(np.uint64) << np.uint64(24)) | \
+                  (idx.astype(np.uint64) & np.uint64(0xFFFFFF))
+            ok = (idx >= 0) & (idx < self.cap)          # all of them without a mistake
+            self.rec_key[idx[ok]] = key[ok]
+            self.rec_flag[idx[ok]] = flag[ok]
+            self.rec_image[idx[ok]] = self.hdr[1] + n
+            pos = valid if gd is None or mistake == "difficult_in_npos" else valid & (np.asarray(gd) == 0)
             np.add.at(self.hdr, 4 + gl[pos], 1)
-        self.hdr[0] = nrec
+        self.hdr[0] = nrec + total
         self.hdr[1] += N
 
-    def ap(self, use_07_metric=False):
-        """-> (ap [C], map, sorted_key [n_records], records per class [C])."""
-        n = int(self.hdr[0])
-        sk = np.sort(self.rec_key[:n])                       # keys are distinct
-        fl = self.rec_flag[(sk & np.uint64(0xFFFFFF)).astype(np.int64)]
+    def ap(self, use_07_metric=False, mistake=None, n_records=None):
+        """-> (ap [C], map, sorted_key [n_records], records per class [C]).  ``n_records``
+        (default hdr[0]): only the first n_records records count."""
+        n = int(self.hdr[0]) if n_records is None else int(n_records)
+        key = self.rec_key[:n]
+        if mistake == "unstable_sort":                       # equal (class, score): the later record first
+            sk = key[np.lexsort((-(key & np.uint64(0xFFFFFF)).astype(np.int64), key >> np.uint64(24)))]
+        else:
+            sk = np.sort(key)                                # keys are distinct
+        ri = (sk & np.uint64(0xFFFFFF)).astype(np.int64)
+        fl = np.where(ri < n, self.rec_flag[np.minimum(ri, self.cap - 1)], -1)   # a key that is no record: ignored
         kc = (sk >> np.uint64(56)).astype(np.int64)
         ap = np.full(self.C, np.nan)
         for c in range(1, self.C):
@@ -133,19 +180,27 @@ class State:
             if npos == 0:
                 continue
             f = fl[kc == c]
-            tp = np.cumsum(f == 1)
-            fp = np.cumsum(f == 0)
+            if len(f) == 0 and mistake == "empty_class_is_nan":
+                continue
+            tp = _running(f == 1, mistake)
+            fp = _running(f == 0, mistake)
             rec = tp / float(npos)
-            prec = tp / np.maximum(tp + fp, 1).astype(np.float64)
+            if mistake == "no_division_guard":
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    prec = tp / (tp + fp).astype(np.float64)
+            else:
+                prec = tp / np.maximum(tp + fp, 1).astype(np.float64)
             if use_07_metric:
                 a = 0.0
                 for i in range(11):
-                    m = prec[rec >= i * 0.1]
+                    m = prec[rec >= (i / 10 if mistake == "tenths_by_division" else i * 0.1)]
                     a = a + (m.max() if m.size else 0.0) / 11.0
             else:
                 mrec = np.concatenate([[0.0], rec, [1.0]])
                 mpre = np.concatenate([[0.0], prec, [0.0]])
                 mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+                if mistake in ("envelope_restarts_each_chunk", "envelope_restarts_each_chunk_from_end"):
+                    mpre[1:-1] = _chunk_envelope(prec, from_end=mistake.endswith("from_end"))
                 i = np.nonzero(mrec[1:] != mrec[:-1])[0]
                 a = float(np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1]))
             ap[c] = a
@@ -154,6 +209,29 @@ class State:
             if ap[c] == ap[c]:
                 s, k = s + ap[c], k + 1
         return ap, (s / k if k else float("nan")), sk, np.bincount(kc, minlength=self.C)
+
+
+def _chunks(n, from_end):
+    """[lo, hi) of the chunks of CHUNK records of an n-record segment, counted from its first
+    record or (``from_end``, the direction ev_pr_walk walks in) from its last."""
+    cuts = sorted({0, n} | set(range(n % CHUNK if from_end else 0, n, CHUNK)))
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+def _running(hit, mistake=None):
+    """Running count of ``hit`` over a segment; the two ``running_sum_restarts_each_chunk``
+    mistakes start again from 0 at every chunk."""
+    if mistake in ("running_sum_restarts_each_chunk", "running_sum_restarts_each_chunk_from_end") and len(hit):
+        return np.concatenate([np.cumsum(hit[lo:hi]) for lo, hi in _chunks(len(hit), mistake.endswith("from_end"))])
+    return np.cumsum(hit)
+
+
+def _chunk_envelope(prec, from_end):
+    """The suffix maximum of ``prec`` restarted at every chunk."""
+    out = np.zeros(len(prec))
+    for lo, hi in _chunks(len(prec), from_end):
+        out[lo:hi] = np.maximum(np.maximum.accumulate(prec[lo:hi][::-1])[::-1], 0.0)
+    return out
 
 
 # ------------------------------------------------------------------ generator
