@@ -925,6 +925,62 @@ int frcnn_coco_eval_accumulate(int C, int64_t n_records, const int64_t* hdr, con
                                double* recall, double* stats, double* ap_per_class, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* Mask overlap counts (DESIGN.md "COCO segm evaluation"; no reference
+ * counterpart): what iouType "segm" needs of a batch of pasted masks.
+ *   det_masks uint8 [N,D,H,W], gt_masks uint8 [N,G,H,W]: one canvas, device,
+ *             16-byte aligned; a pixel is set iff its byte is non-zero
+ *   det_count int32 [N] or NULL (every row is a detection), clamped to [0, D]
+ *   det_labels int32 [N,D] and gt_labels int32 [N,G], or both NULL
+ *   inter     int32 [N,D,G]: pixels set in both masks of a considered pair, 0
+ *             for every other pair.  With labels a pair is considered iff
+ *             d < det_count[n] and det_labels[n,d] == gt_labels[n,g] and that
+ *             label is in [1, C); without, iff d < det_count[n].
+ *   det_area  int32 [N,D]: pixels set, 0 for d >= det_count[n] (not read)
+ *   gt_area   int32 [N,G]: pixels set
+ * Limits: 1 <= N <= 1024, 1 <= D <= 1024, 0 <= G <= 256, 1 <= H, W <= 4096 with
+ * H*W <= 2^24, 2 <= C <= 128 (read with labels only).  Every output element is
+ * stored exactly once; integers only, so two calls give the same bits.
+ * Workspace: frcnn_mask_overlap_workspace_size bytes (0 outside the limits): the
+ * masks as bits, one 64-bit word per 64 pixels of a row, and per mask its pixel
+ * count and its window of non-empty rows and word columns. */
+size_t frcnn_mask_overlap_workspace_size(int N, int D, int G, int H, int W);
+int frcnn_mask_overlap(int N, int D, int G, int H, int W, int C, const uint8_t* det_masks,
+                       const uint8_t* gt_masks, const int32_t* det_labels, const int32_t* det_count,
+                       const int32_t* gt_labels, int32_t* inter, int32_t* det_area, int32_t* gt_area,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* The launch shape of frcnn_mask_overlap.  Host only: no HIP call is made.
+ *   plan[0] 64-bit words per row, plan[1] the pack branch: 0 whole 16-byte
+ *   vectors (W % 16 == 0), 1 rows with an unaligned head and a tail
+ *   plan[2] pack workgroups (one per mask), plan[3] pair workgroups (one per
+ *   (image, detection)), plan[4] workspace bytes
+ *   plan[5] 16-bit patterns per row, plan[6] rows per band, plan[7] bands per mask */
+int frcnn_mask_overlap_plan(int N, int D, int G, int H, int W, int64_t plan[8]);
+
+/* The kernels of a frcnn_mask_overlap call on an H x W canvas and the pack branch,
+ * "mo_pack_kernel[vec16]+mo_pair_kernel" or "...[vec16+edges]...".  Host only. */
+int frcnn_mask_overlap_kernel(int H, int W, char* name, size_t len);
+
+/* frcnn_coco_eval_update with iouType "segm" (DESIGN.md "COCO segm evaluation"):
+ * the same records, appended to the same state, from the counts of
+ * frcnn_mask_overlap's labelled form instead of boxes.
+ *   inter int32 [N,M,G], det_pixels int32 [N,M], gt_pixels int32 [N,G]
+ *   gt_area double [N,G] or NULL: the annotation's area, which the size ranges
+ *         and the ignore rule see instead of the pixel count
+ * IoU of a pair: 0 when inter == 0; inter / det_pixels for a crowd gt; else
+ * inter / (det_pixels + gt_pixels - inter): exact integers, one fp64 division.
+ * A detection's area is det_pixels.  Everything else is frcnn_coco_eval_update's. */
+int frcnn_coco_segm_eval_update(int N, int M, int G, int C, int64_t cap, const int32_t* det_labels,
+                                const float* det_scores, const int32_t* det_count, const int32_t* inter,
+                                const int32_t* det_pixels, const int32_t* gt_pixels,
+                                const int32_t* gt_labels, const uint8_t* gt_crowd, const double* gt_area,
+                                const double* tables, int64_t* hdr, uint64_t* rec_key, uint64_t* rec_bits,
+                                void* stream);
+
+/* The kernels of an update: "coco_match_kernel<boxes>+coco_advance_kernel" (segm == 0,
+ * frcnn_coco_eval_update) or "coco_match_kernel<counts>+..." (segm == 1).  Host only. */
+int frcnn_coco_eval_kernel(int segm, char* name, size_t len);
+
 /* ------------------------------------------------------------------ losses */
 
 /* The training losses of one stage, train.py:29-57 with :81-83 (RPN) or

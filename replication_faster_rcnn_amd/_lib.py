@@ -144,6 +144,12 @@ SIGNATURES = {
     "frcnn_coco_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, P, P, P, P, P]),
     "frcnn_coco_eval_workspace_size": (SZ, [I32, I64]),
     "frcnn_coco_eval_accumulate": (I32, [I32, I64, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_mask_overlap_workspace_size": (SZ, [I32, I32, I32, I32, I32]),
+    "frcnn_mask_overlap": (I32, [I32, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "frcnn_mask_overlap_plan": (I32, [I32, I32, I32, I32, I32, P]),
+    "frcnn_mask_overlap_kernel": (I32, [I32, I32, ctypes.c_char_p, SZ]),
+    "frcnn_coco_segm_eval_update": (I32, [I32, I32, I32, I32, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "frcnn_coco_eval_kernel": (I32, [I32, ctypes.c_char_p, SZ]),
     "frcnn_losses_workspace_size": (SZ, [I64, I32]),
     "frcnn_losses_fwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, SZ, P]),
     "frcnn_losses_bwd": (I32, [I64, I32, I32, P, P, P, P, I32, F64, P, P, P, P, P, P]),
@@ -418,6 +424,19 @@ def eval_plan(N, M, n_records) -> dict:
     plan = (ctypes.c_int64 * 10)()
     check(lib.frcnn_eval_plan(int(N), int(M), int(n_records), plan), "eval_plan")
     return dict(zip(EVAL_PLAN_FIELDS, plan))
+
+
+MASK_OVERLAP_PLAN_FIELDS = ("words", "edges", "pack_blocks", "pair_blocks", "workspace", "items", "band_rows", "bands")
+
+
+def mask_overlap_plan(N, D, G, H, W) -> dict:
+    """frcnn_mask_overlap_plan: words per row, the pack branch, the workgroups of the two
+    launches, the workspace bytes and the band shape of ``frcnn_mask_overlap``, by
+    MASK_OVERLAP_PLAN_FIELDS.  Host only."""
+    lib = load(require_gpu=False)
+    plan = (ctypes.c_int64 * 8)()
+    check(lib.frcnn_mask_overlap_plan(int(N), int(D), int(G), int(H), int(W), plan), "mask_overlap_plan")
+    return dict(zip(MASK_OVERLAP_PLAN_FIELDS, plan))
 
 
 def set_path(op: str, path) -> None:

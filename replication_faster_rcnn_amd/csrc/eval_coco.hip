@@ -1,8 +1,11 @@
 // COCO-style detection evaluation: AP over IoU 0.50:0.05:0.95, AP by object
 // size, AR at 1 / 10 / 100 detections per image.  The contract is
 // pycocotools.cocoeval with iouType "bbox", restated in DESIGN.md "COCO-style
-// evaluation"; the numpy restatement is tests/coco_eval_ref.py.
-//   coco_match_kernel      : one workgroup per image, the gt staged in LDS.
+// evaluation"; the numpy restatement is tests/coco_eval_ref.py.  With iouType
+// "segm" (DESIGN.md "COCO segm evaluation", tests/coco_segm_ref.py) only the
+// source of a detection's IoU row and of the areas changes: CoBoxes forms them
+// from boxes in fp64, CoCounts from the pixel counts of mask_overlap.hip.
+//   coco_match_kernel<Src> : one workgroup per image, the gt staged in LDS.
 //                            Step one, thread = slot: the slot's rank within
 //                            its (image, class) in (descending score, ascending
 //                            slot) order, counted against every slot of the
@@ -33,6 +36,8 @@
 //                            each: a strided sum and a fixed tree.
 // Integer atomics only (LDS counts, npig); no float atomics: every output is
 // bit-identical from run to run.
+#include <cstdio>
+
 #include "eval_common.h"
 
 namespace frcnn {
@@ -69,19 +74,119 @@ __device__ __forceinline__ void co_wave_sync() {
 }
 
 struct CoGt {
-    double box[kEvMaxG][4];
-    double area[kEvMaxG];
-    int label[kEvMaxG];  // 0 for a row that is not a valid gt
+    double area[kEvMaxG];  // the area the size ranges and the ignore rule see
+    int label[kEvMaxG];    // 0 for a row that is not a valid gt
     unsigned char crowd[kEvMaxG];
 };
 
+// The row source of the matching: what a gt and a detection are, and the IoU of a pair.
+//   Shared               : the source's own LDS
+//   load_gt(sh, t, g)    : stage gt row g (of the batch) as the image's gt t; returns its area for the ranges
+//   stage(sh, wid, lane, nd, order, drow) : the wave's nd ranked detections, before its walk
+//   det(sh, wid, r, row) : the detection of rank r (row of the batch); .area is its area for the ranges
+//   iou(sh, d, t, crowd, garea) : fp64 IoU of that detection and the image's gt t
+struct CoBoxes {  // iouType "bbox"
+    struct Shared {
+        double box[kEvMaxG][4];
+        float dbox[kEvWaves][kCoKeep][4];  // the boxes of a wave's detections, by rank
+    };
+    struct Det {
+        double d0, d1, d2, d3, area;
+    };
+    const float* __restrict__ det_boxes;
+    const double* __restrict__ gt_boxes;
+
+    __device__ __forceinline__ double load_gt(Shared& sh, int t, size_t g) const {
+        const double* b = gt_boxes + g * 4;
+        sh.box[t][0] = b[0];
+        sh.box[t][1] = b[1];
+        sh.box[t][2] = b[2];
+        sh.box[t][3] = b[3];
+        const double h = b[2] - b[0], w = b[3] - b[1];
+        return h * w;
+    }
+    __device__ __forceinline__ void stage(Shared& sh, int wid, int lane, int nd, const int* order, size_t drow) const {
+        for (int r = lane; r < nd; r += kWave) {
+            const float4 b = *reinterpret_cast<const float4*>(det_boxes + (drow + order[r]) * 4);
+            sh.dbox[wid][r][0] = b.x;
+            sh.dbox[wid][r][1] = b.y;
+            sh.dbox[wid][r][2] = b.z;
+            sh.dbox[wid][r][3] = b.w;
+        }
+    }
+    __device__ __forceinline__ Det det(const Shared& sh, int wid, int r, size_t) const {
+        const float* db = sh.dbox[wid][r];
+        Det d;
+        d.d0 = static_cast<double>(db[0]);
+        d.d1 = static_cast<double>(db[1]);
+        d.d2 = static_cast<double>(db[2]);
+        d.d3 = static_cast<double>(db[3]);
+        const double dh = d.d2 - d.d0, dw = d.d3 - d.d1;
+        d.area = dh * dw;
+        return d;
+    }
+    __device__ __forceinline__ double iou(const Shared& sh, const Det& d, int g, bool crowd, double garea) const {
+        const double ih = (d.d2 < sh.box[g][2] ? d.d2 : sh.box[g][2]) - (d.d0 > sh.box[g][0] ? d.d0 : sh.box[g][0]);
+        const double iw = (d.d3 < sh.box[g][3] ? d.d3 : sh.box[g][3]) - (d.d1 > sh.box[g][1] ? d.d1 : sh.box[g][1]);
+        double v = 0.0;
+        if (!(ih <= 0.0) && !(iw <= 0.0)) {
+            const double i = ih * iw;
+            if (crowd) {
+                v = i / d.area;
+            } else {
+                double u = d.area + garea;
+                u = u - i;
+                v = i / u;
+            }
+        }
+        return v;
+    }
+};
+
+struct CoCounts {  // iouType "segm": maskApi.c's rleIou on the counts of frcnn_mask_overlap
+    struct Shared {
+        int pix[kEvMaxG];  // the gt's pixel count: the union's term, whatever gt_area says
+    };
+    struct Det {
+        const int32_t* irow;  // inter[n, slot, :]
+        int pix;
+        double area;
+    };
+    int G;
+    const int32_t* __restrict__ inter;     // [N, M, G]
+    const int32_t* __restrict__ det_pix;   // [N, M]
+    const int32_t* __restrict__ gt_pix;    // [N, G]
+    const double* __restrict__ gt_area;    // [N, G] or null: the annotation's area field
+
+    __device__ __forceinline__ double load_gt(Shared& sh, int t, size_t g) const {
+        const int p = gt_pix[g];
+        sh.pix[t] = p;
+        return gt_area ? gt_area[g] : static_cast<double>(p);
+    }
+    __device__ __forceinline__ void stage(Shared&, int, int, int, const int*, size_t) const {}
+    __device__ __forceinline__ Det det(const Shared&, int, int, size_t row) const {
+        Det d;
+        d.irow = inter + row * G;
+        d.pix = det_pix[row];
+        d.area = static_cast<double>(d.pix);
+        return d;
+    }
+    __device__ __forceinline__ double iou(const Shared& sh, const Det& d, int g, bool crowd, double) const {
+        const int i = d.irow[g];
+        if (i == 0) return 0.0;
+        const int u = crowd ? d.pix : d.pix + sh.pix[g] - i;  // both counts <= 2^24
+        return static_cast<double>(i) / static_cast<double>(u);
+    }
+};
+
+template <class Src>
 __global__ __launch_bounds__(kEvThreads) void coco_match_kernel(
-    int N, int M, int G, int C, long long cap, const float* __restrict__ det_boxes,
-    const int32_t* __restrict__ det_labels, const float* __restrict__ det_scores,
-    const int32_t* __restrict__ det_count, const double* __restrict__ gt_boxes,
+    int N, int M, int G, int C, long long cap, const Src src, const int32_t* __restrict__ det_labels,
+    const float* __restrict__ det_scores, const int32_t* __restrict__ det_count,
     const int32_t* __restrict__ gt_labels, const uint8_t* __restrict__ gt_crowd, const double* __restrict__ tables,
     long long* hdr, uint64_t* __restrict__ rec_key, uint64_t* rec_bits) {
     __shared__ CoGt gt;
+    __shared__ typename Src::Shared sh;
     __shared__ unsigned int cpig[kEvMaxC * kCoA];
     __shared__ unsigned int dcnt[kEvMaxC];  // detections of the class with a rank below 100
     __shared__ long long red[2 * kEvWaves];
@@ -89,7 +194,6 @@ __global__ __launch_bounds__(kEvThreads) void coco_match_kernel(
     __shared__ double row[kEvWaves][kEvMaxG];
     __shared__ int members[kEvWaves][kEvMaxG];
     __shared__ int order[kEvWaves][kCoKeep];
-    __shared__ float dbox[kEvWaves][kCoKeep][4];  // the boxes of those detections, by rank
     __shared__ unsigned short slot_info[kCoSlotTable];  // class << 8 | rank of the image's first 4,096 slots
     __shared__ int next_class;
 
@@ -106,13 +210,7 @@ __global__ __launch_bounds__(kEvThreads) void coco_match_kernel(
         const size_t g = static_cast<size_t>(n) * G + tid;
         const int l = gt_labels[g];
         const bool valid = l >= 1 && l < C;
-        const double* b = gt_boxes + g * 4;
-        gt.box[tid][0] = b[0];
-        gt.box[tid][1] = b[1];
-        gt.box[tid][2] = b[2];
-        gt.box[tid][3] = b[3];
-        const double h = b[2] - b[0], w = b[3] - b[1];
-        gt.area[tid] = h * w;
+        gt.area[tid] = src.load_gt(sh, tid, g);
         gt.label[tid] = valid ? l : 0;
         gt.crowd[tid] = (gt_crowd && gt_crowd[g]) ? 1 : 0;
     }
@@ -210,13 +308,7 @@ __global__ __launch_bounds__(kEvThreads) void coco_match_kernel(
             if (rank < kCoKeep) order[wid][rank] = s;
         }
         co_wave_sync();
-        for (int r = lane; r < nd; r += kWave) {
-            const float4 b = *reinterpret_cast<const float4*>(det_boxes + (drow + order[wid][r]) * 4);
-            dbox[wid][r][0] = b.x;
-            dbox[wid][r][1] = b.y;
-            dbox[wid][r][2] = b.z;
-            dbox[wid][r][3] = b.w;
-        }
+        src.stage(sh, wid, lane, nd, order[wid], drow);
         int nc = 0;  // the class's gt in slot order
         for (int g0 = 0; g0 < G; g0 += kWave) {
             const int g = g0 + lane;
@@ -229,27 +321,11 @@ __global__ __launch_bounds__(kEvThreads) void coco_match_kernel(
         uint64_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;  // gt taken at this lane's (range, threshold)
         for (int r = 0; r < nd; ++r) {
             const int s = order[wid][r];
-            const float* db = dbox[wid][r];
-            const double d0 = static_cast<double>(db[0]), d1 = static_cast<double>(db[1]);
-            const double d2 = static_cast<double>(db[2]), d3 = static_cast<double>(db[3]);
-            const double dh = d2 - d0, dw = d3 - d1;
-            const double area_d = dh * dw;
+            const typename Src::Det dv = src.det(sh, wid, r, drow + s);
+            const double area_d = dv.area;
             for (int j = lane; j < nc; j += kWave) {
                 const int g = members[wid][j];
-                const double ih = (d2 < gt.box[g][2] ? d2 : gt.box[g][2]) - (d0 > gt.box[g][0] ? d0 : gt.box[g][0]);
-                const double iw = (d3 < gt.box[g][3] ? d3 : gt.box[g][3]) - (d1 > gt.box[g][1] ? d1 : gt.box[g][1]);
-                double v = 0.0;
-                if (!(ih <= 0.0) && !(iw <= 0.0)) {
-                    const double i = ih * iw;
-                    if (gt.crowd[g]) {
-                        v = i / area_d;
-                    } else {
-                        double u = area_d + gt.area[g];
-                        u = u - i;
-                        v = i / u;
-                    }
-                }
-                row[wid][j] = v;
+                row[wid][j] = src.iou(sh, dv, g, gt.crowd[g] != 0, gt.area[g]);
             }
             co_wave_sync();
             bool matched = false, ign = false;
@@ -486,12 +562,49 @@ extern "C" int frcnn_coco_eval_update(int N, int M, int G, int C, int64_t cap, c
     FRCNN_REQUIRE(hdr && rec_key && rec_bits, "frcnn_coco_eval_update: null state (hdr / rec_key / rec_bits)");
     hipStream_t st = as_stream(stream);
     long long* h = reinterpret_cast<long long*>(hdr);
-    coco_match_kernel<<<N, kEvThreads, 0, st>>>(N, M, G, C, static_cast<long long>(cap), det_boxes, det_labels,
-                                                det_scores, det_count, gt_boxes, gt_labels, gt_crowd, tables, h,
-                                                rec_key, rec_bits);
+    coco_match_kernel<CoBoxes><<<N, kEvThreads, 0, st>>>(N, M, G, C, static_cast<long long>(cap),
+                                                         CoBoxes{det_boxes, gt_boxes}, det_labels, det_scores,
+                                                         det_count, gt_labels, gt_crowd, tables, h, rec_key, rec_bits);
     FRCNN_LAUNCH_CHECK("coco_match_kernel");
     coco_advance_kernel<<<1, kEvThreads, 0, st>>>(N, M, static_cast<long long>(cap), det_count, h);
     FRCNN_LAUNCH_CHECK("coco_advance_kernel");
+    return FRCNN_OK;
+}
+
+extern "C" int frcnn_coco_segm_eval_update(int N, int M, int G, int C, int64_t cap, const int32_t* det_labels,
+                                           const float* det_scores, const int32_t* det_count, const int32_t* inter,
+                                           const int32_t* det_pixels, const int32_t* gt_pixels,
+                                           const int32_t* gt_labels, const uint8_t* gt_crowd, const double* gt_area,
+                                           const double* tables, int64_t* hdr, uint64_t* rec_key, uint64_t* rec_bits,
+                                           void* stream) {
+    const char* who = "frcnn_coco_segm_eval_update";
+    FRCNN_REQUIRE(N >= 1 && N <= kEvMaxN, "%s: N=%d must be in [1, %d]", who, N, kEvMaxN);
+    FRCNN_REQUIRE(M >= 1 && M <= kEvMaxM, "%s: M=%d must be in [1, %d]", who, M, kEvMaxM);
+    FRCNN_REQUIRE(G >= 0 && G <= kEvMaxG, "%s: G=%d must be in [0, %d]", who, G, kEvMaxG);
+    FRCNN_REQUIRE(C >= 2 && C <= kEvMaxC, "%s: C=%d must be in [2, %d]", who, C, kEvMaxC);
+    FRCNN_REQUIRE(cap >= 1 && cap <= kEvMaxCap, "%s: cap=%lld must be in [1, %lld]", who, static_cast<long long>(cap),
+                  static_cast<long long>(kEvMaxCap));
+    FRCNN_REQUIRE(det_labels && det_scores && det_count && det_pixels,
+                  "%s: null input (det_labels / det_scores / det_count / det_pixels)", who);
+    FRCNN_REQUIRE(G == 0 || (inter && gt_pixels && gt_labels), "%s: null input (inter / gt_pixels / gt_labels)", who);
+    FRCNN_REQUIRE(tables, "%s: null tables", who);
+    FRCNN_REQUIRE(hdr && rec_key && rec_bits, "%s: null state (hdr / rec_key / rec_bits)", who);
+    hipStream_t st = as_stream(stream);
+    long long* h = reinterpret_cast<long long*>(hdr);
+    coco_match_kernel<CoCounts><<<N, kEvThreads, 0, st>>>(N, M, G, C, static_cast<long long>(cap),
+                                                          CoCounts{G, inter, det_pixels, gt_pixels, gt_area},
+                                                          det_labels, det_scores, det_count, gt_labels, gt_crowd,
+                                                          tables, h, rec_key, rec_bits);
+    FRCNN_LAUNCH_CHECK("coco_match_kernel");
+    coco_advance_kernel<<<1, kEvThreads, 0, st>>>(N, M, static_cast<long long>(cap), det_count, h);
+    FRCNN_LAUNCH_CHECK("coco_advance_kernel");
+    return FRCNN_OK;
+}
+
+extern "C" int frcnn_coco_eval_kernel(int segm, char* name, size_t len) {
+    FRCNN_REQUIRE(name && len > 0, "frcnn_coco_eval_kernel: null name buffer");
+    FRCNN_REQUIRE(segm == 0 || segm == 1, "frcnn_coco_eval_kernel: segm must be 0 (bbox) or 1, got %d", segm);
+    std::snprintf(name, len, "coco_match_kernel<%s>+coco_advance_kernel", segm ? "counts" : "boxes");
     return FRCNN_OK;
 }
 

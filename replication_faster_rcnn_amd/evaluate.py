@@ -17,6 +17,9 @@ allocation, no host read -- and ``result`` closes the dataset with
 "COCO-style evaluation"): AP averaged over IoU 0.50:0.05:0.95, AP50, AP75, AP
 for small / medium / large objects and AR at 1 / 10 / 100 detections per image,
 on ``ops.coco_eval_update`` and ``ops.coco_eval_accumulate``.
+``COCOMaskEvaluator`` scores a mask head the same way with iouType "segm"
+(DESIGN.md "COCO segm evaluation"), on ``ops.mask_overlap`` and
+``ops.coco_segm_eval_update``.
 """
 from __future__ import annotations
 
@@ -139,3 +142,42 @@ class COCOEvaluator:
                    n_records=int(hdr[0]), n_images=int(hdr[1]))
         out.update({name: float(v) for name, v in zip(COCO_STATS, stats)})
         return out
+
+
+class COCOMaskEvaluator(COCOEvaluator):
+    """``COCOEvaluator`` with iouType "segm" (DESIGN.md "COCO segm evaluation"): a
+    detection is matched by the IoU of its pasted mask with the gt masks, and
+    its area is its pixel count.  The records, ``reset`` and ``result`` are the
+    parent's."""
+
+    def __init__(self, n_class: int = 21, capacity: int = 1 << 20):
+        super().__init__(n_class, capacity)
+        self._out = {}   # (N, D, G) -> the MaskOverlap a batch of that shape writes
+
+    def update(self, det, det_masks, gt_masks, gt_labels, gt_crowd=None, gt_area=None) -> None:
+        """One batch.  ``det``: ``(labels, scores, count)`` or a ``BoxDetections``;
+        ``det_masks`` uint8 [N, D, H, W] as ``ops.mask_head_paste`` returns them with
+        a threshold; ``gt_masks`` uint8 [N, G, H, W] on the same canvas (any non-zero
+        byte is a set pixel); ``gt_labels`` [N, G], ``gt_crowd`` [N, G] or None,
+        ``gt_area`` [N, G] or None: the annotations' ``area`` field, which decides
+        the size range of a gt instead of its pixel count.  numpy arrays and CPU
+        tensors are moved to the device.  Nothing is read back."""
+        if isinstance(det, ops.BoxDetections):
+            det = (det.labels, det.scores, det.count)
+        if len(det) != 3:
+            raise RuntimeError("COCOMaskEvaluator.update: det must be (labels, scores, count) or a BoxDetections")
+        labels, scores, count = (_dev(t, dt) for t, dt in zip(det, (torch.int32, torch.float32, torch.int32)))
+        det_masks, gt_masks = _dev(det_masks, torch.uint8), _dev(gt_masks, torch.uint8)
+        gt_labels = _dev(gt_labels, torch.int32)
+        key = (det_masks.shape[0], det_masks.shape[1], gt_masks.shape[1], det_masks.device)
+        out = self._out.get(key)
+        if out is None:
+            N, D, G, dev = key
+            out = self._out[key] = tuple(torch.empty(s, dtype=torch.int32, device=dev)
+                                         for s in ((N, D, G), (N, D), (N, G)))
+        overlap = ops.mask_overlap(det_masks, gt_masks, det_labels=labels, det_count=count, gt_labels=gt_labels,
+                                   n_class=self.n_class, out=out)
+        ops.coco_segm_eval_update((labels, scores, count), overlap, gt_labels,
+                                  None if gt_crowd is None else _dev(gt_crowd, torch.uint8),
+                                  gt_area=None if gt_area is None else _dev(gt_area, torch.float64),
+                                  state=self.state)

@@ -44,6 +44,10 @@
 * ``coco_eval_update(...)`` / ``coco_eval_accumulate(...)`` -- the COCO protocol
   on the same inputs: AP over IoU 0.50:0.95, by object size, AR at 1 / 10 / 100
   detections (DESIGN.md "COCO-style evaluation").
+* ``mask_overlap(...)`` / ``coco_segm_eval_update(...)`` -- the same protocol with
+  iouType "segm" on ``mask_head_paste``'s masks: pixel counts of the masks and of
+  their intersections, then the matching on those counts (DESIGN.md §3 "COCO segm
+  evaluation").
 * ``rpn_losses(...)`` / ``head_losses(...)`` -- the four training losses of
   train.py:29-57, :81-83, :112-121, fused, with their own backward (DESIGN.md
   "Losses").
@@ -70,7 +74,7 @@ Two input rules (tests/test_gpu_wrapper_inputs.py):
   (both of one dtype): ``cls_nhwc`` / ``reg_nhwc`` come back in that dtype.
 * The hot-path ops on device tensors (``propose``, ``propose_multilevel``, ``rpn_targets_multilevel``,
   ``rpn_losses_multilevel``, ``box_head_targets``, ``box_head_losses``, ``box_head_detections``, ``roi_transform``,
-  ``detect``, ``eval_update``, ``coco_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
+  ``detect``, ``eval_update``, ``coco_eval_update``, ``mask_overlap``, ``coco_segm_eval_update``, ``rpn_losses``, ``head_losses``, ``preprocess``,
   ``rescale_boxes``) convert nothing: every tensor must already be a
   contiguous device tensor of the documented dtype and exact shape, checked by
   attribute reads alone (no copy, no synchronisation) before any launch.
@@ -2199,6 +2203,156 @@ def coco_eval_accumulate(state, n_records: int = None, *, workspace=None):
                                               _lib.ptr(precision), _lib.ptr(recall), _lib.ptr(stats), _lib.ptr(apc),
                                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "coco_eval_accumulate")
     return precision, recall, stats, apc
+
+
+# ------------------------------------------------------ COCO segm evaluation
+MASK_OVERLAP_MAX_N, MASK_OVERLAP_MAX_D, MASK_OVERLAP_MAX_G, MASK_OVERLAP_MAX_DIM = 1024, 1024, 256, 4096
+MASK_OVERLAP_MAX_PIXELS, MASK_OVERLAP_MAX_C = 1 << 24, 128
+MaskOverlap = collections.namedtuple("MaskOverlap", "inter det_area gt_area")
+_mo_ws = {}   # (N, D, G, H, W) -> workspace bytes
+
+
+def mask_overlap_kernel(canvas_h, canvas_w) -> str:
+    """frcnn_mask_overlap_kernel: the two kernels of a ``mask_overlap`` call and the pack
+    kernel's plan branch ("vec16": every row is whole 16-byte vectors; "+edges": rows have
+    an unaligned head or a tail).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    return _mh_name(lib.frcnn_mask_overlap_kernel, "mask_overlap_kernel", int(canvas_h), int(canvas_w))
+
+
+def coco_eval_kernel(segm: bool = False) -> str:
+    """frcnn_coco_eval_kernel: the kernels of ``coco_eval_update`` (boxes) or, with ``segm``,
+    of ``coco_segm_eval_update`` (counts).  Host only."""
+    lib = _lib.load(require_gpu=False)
+    return _mh_name(lib.frcnn_coco_eval_kernel, "coco_eval_kernel", int(bool(segm)))
+
+
+def mask_overlap_workspace_size(N, D, G, H, W) -> int:
+    """frcnn_mask_overlap_workspace_size (0 outside the limits).  Host only."""
+    return int(_lib.load(require_gpu=False).frcnn_mask_overlap_workspace_size(int(N), int(D), int(G), int(H), int(W)))
+
+
+def mask_overlap(det_masks, gt_masks, *, det_labels=None, det_count=None, gt_labels=None, n_class=None, out=None,
+                 workspace=None):
+    """Pixel counts of a batch of masks and of their pairwise intersections
+    (frcnn_mask_overlap; DESIGN.md "COCO segm evaluation" is the contract).
+
+    ``det_masks`` uint8 [N, D, H, W] (``mask_head_paste``'s with a threshold) and ``gt_masks``
+    uint8 [N, G, H, W] on the same canvas; a pixel is set iff its byte is non-zero.
+    ``det_count`` int32 [N] (None: every row is a detection).  With ``det_labels`` int32
+    [N, D], ``gt_labels`` int32 [N, G] and ``n_class`` a pair is considered iff d <
+    det_count[n], the labels are equal and in [1, n_class); without labels every pair with
+    d < det_count[n] is.
+
+    Returns ``MaskOverlap(inter int32 [N, D, G], det_area int32 [N, D], gt_area int32 [N, G])``:
+    ``inter`` is 0 for a pair that is not considered, ``det_area`` 0 at or beyond ``det_count``
+    (those masks are not read).  Exact, and the same bits from call to call.
+
+    A hot-path op: nothing is converted; a wrong dtype, shape, device, canvas or a strided view
+    raises RuntimeError naming the argument before any launch.  ``out``: the three outputs,
+    caller-owned; ``workspace``: a uint8 device tensor of at least
+    ``mask_overlap_workspace_size`` bytes."""
+    op = "mask_overlap"
+    lib = _lib.load()
+    for name, t in (("det_masks", det_masks), ("gt_masks", gt_masks)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise RuntimeError(f"{op}: {name} must be a uint8 device tensor of shape [N, {name[0].upper()}, H, W]")
+    N, D, H, W = (int(v) for v in det_masks.shape)
+    G = int(gt_masks.shape[1])
+    if tuple(gt_masks.shape[2:]) != (H, W):
+        raise RuntimeError(f"{op}: gt_masks: canvas {tuple(gt_masks.shape[2:])} is not det_masks' canvas {(H, W)}")
+    if not (1 <= N <= MASK_OVERLAP_MAX_N and 1 <= D <= MASK_OVERLAP_MAX_D and 0 <= G <= MASK_OVERLAP_MAX_G
+            and 1 <= H <= MASK_OVERLAP_MAX_DIM and 1 <= W <= MASK_OVERLAP_MAX_DIM
+            and H * W <= MASK_OVERLAP_MAX_PIXELS):
+        raise RuntimeError(f"{op}: det_masks / gt_masks: N={N} must be in [1, {MASK_OVERLAP_MAX_N}], D={D} in "
+                           f"[1, {MASK_OVERLAP_MAX_D}], G={G} in [0, {MASK_OVERLAP_MAX_G}], H={H} and W={W} in "
+                           f"[1, {MASK_OVERLAP_MAX_DIM}] with H*W <= 2^24")
+    _require(op, "det_masks", det_masks, torch.uint8, (N, D, H, W))
+    _require(op, "gt_masks", gt_masks, torch.uint8, (N, G, H, W))
+    if (det_labels is None) != (gt_labels is None):
+        raise RuntimeError(f"{op}: det_labels and gt_labels are given together or not at all")
+    C = 0
+    if det_labels is not None:
+        if n_class is None or not 2 <= int(n_class) <= MASK_OVERLAP_MAX_C:
+            raise RuntimeError(f"{op}: n_class must be in [2, {MASK_OVERLAP_MAX_C}] with labels; got {n_class}")
+        C = int(n_class)
+        _require(op, "det_labels", det_labels, torch.int32, (N, D))
+        _require(op, "gt_labels", gt_labels, torch.int32, (N, G))
+    if det_count is not None:
+        _require(op, "det_count", det_count, torch.int32, (N,))
+    dev = det_masks.device
+    for name, t in (("gt_masks", gt_masks), ("det_labels", det_labels), ("det_count", det_count),
+                    ("gt_labels", gt_labels)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{op}: {name} is on {t.device} but det_masks on {dev}")
+    if det_masks.data_ptr() % 16 or gt_masks.data_ptr() % 16:
+        raise RuntimeError(f"{op}: det_masks / gt_masks must be 16-byte aligned (a view into a larger tensor?)")
+    shapes = ((N, D, G), (N, D), (N, G))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int32, device=dev) for s in shapes)
+    else:
+        if len(out) != 3:
+            raise RuntimeError(f"{op}: out must be (inter, det_area, gt_area)")
+        for name, t, s in zip(MaskOverlap._fields, out, shapes):
+            _require(op, f"out.{name}", t, torch.int32, s)
+    key = (N, D, G, H, W)
+    need = _mo_ws.get(key)
+    if need is None:
+        need = _mo_ws[key] = int(lib.frcnn_mask_overlap_workspace_size(N, D, G, H, W))
+    ws = workspace if workspace is not None else _lib.cached_workspace(op, need, dev)
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_cuda or ws.numel() < need:
+        raise RuntimeError(f"{op}: workspace must be a uint8 device tensor of at least {need} B")
+    _lib.check(lib.frcnn_mask_overlap(N, D, G, H, W, C, _lib.ptr(det_masks), _lib.ptr(gt_masks),
+                                      _lib.ptr(det_labels), _lib.ptr(det_count), _lib.ptr(gt_labels),
+                                      _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_ptr()), op)
+    return MaskOverlap(*out)
+
+
+def coco_segm_eval_update(det, overlap, gt_labels: torch.Tensor, gt_crowd: torch.Tensor = None, *,
+                          gt_area: torch.Tensor = None, state) -> None:
+    """``coco_eval_update`` with iouType "segm" (frcnn_coco_segm_eval_update; DESIGN.md "COCO
+    segm evaluation"): the same records into the same ``state``, so ``coco_eval_accumulate``
+    closes it unchanged -- stream-ordered, no allocation, no host synchronisation.
+
+    ``det`` is ``(labels, scores, count)`` or a ``BoxDetections``; ``overlap`` the
+    ``MaskOverlap`` of ``mask_overlap``'s labelled form for the same labels and count.  The IoU of
+    a pair is 0 without a common pixel, ``i / a_d`` against a crowd gt and ``i / (a_d + a_g - i)``
+    otherwise; a detection's area is its pixel count; a gt's area for the size ranges is
+    ``gt_area`` (fp64 [N, G], the annotation's field) when given, else its pixel count."""
+    op = "coco_segm_eval_update"
+    lib = _lib.load()
+    if isinstance(det, BoxDetections):
+        labels, scores, count = det.labels, det.scores, det.count
+    elif len(det) == 3:
+        labels, scores, count = det
+    else:
+        raise RuntimeError(f"{op}: det must be (labels, scores, count) or a BoxDetections")
+    if not isinstance(overlap, tuple) or len(overlap) != 3:
+        raise RuntimeError(f"{op}: overlap must be ops.mask_overlap's MaskOverlap")
+    inter, det_pix, gt_pix = overlap
+    C, cap = _coco_state_check(state, op)
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 2 or not isinstance(gt_labels, torch.Tensor) \
+            or gt_labels.dim() != 2:
+        raise RuntimeError(f"{op}: det labels must be [N, M] and gt_labels [N, G]")
+    N, M = (int(v) for v in labels.shape)
+    G = int(gt_labels.shape[1])
+    ins = [("det.labels", labels, torch.int32, (N, M)), ("det.scores", scores, torch.float32, (N, M)),
+           ("det.count", count, torch.int32, (N,)), ("overlap.inter", inter, torch.int32, (N, M, G)),
+           ("overlap.det_area", det_pix, torch.int32, (N, M)), ("overlap.gt_area", gt_pix, torch.int32, (N, G)),
+           ("gt_labels", gt_labels, torch.int32, (N, G))]
+    if gt_crowd is not None:
+        ins.append(("gt_crowd", gt_crowd, torch.uint8, (N, G)))
+    if gt_area is not None:
+        ins.append(("gt_area", gt_area, torch.float64, (N, G)))
+    for name, t, dt, shape in ins:
+        _require(op, name, t, dt, shape)
+    hdr, key, bits, tables = state
+    _lib.check(lib.frcnn_coco_segm_eval_update(N, M, G, C, cap, _lib.ptr(labels), _lib.ptr(scores), _lib.ptr(count),
+                                               _lib.ptr(inter), _lib.ptr(det_pix), _lib.ptr(gt_pix),
+                                               _lib.ptr(gt_labels), _lib.ptr(gt_crowd), _lib.ptr(gt_area),
+                                               _lib.ptr(tables), _lib.ptr(hdr), _lib.ptr(key), _lib.ptr(bits),
+                                               _lib.stream_ptr()), op)
 
 
 # ------------------------------------------------------------- RPN epilogue
